@@ -7,7 +7,7 @@ all-reduce of the flat gradient bucket) -> fused Adam (+bf16 weight re-pack), i.
 reference training step (utils.py:346-374), nothing skipped.  Weights are random-init of the exact
 reference architecture; data is synthetic DAS time-space matrices of the paper's shape (1x100x250).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,6 +17,12 @@ and exits with the first failing rank's status; under torchrun each process is o
 
 Weak scaling: per-GPU batch fixed at 32, global batch 32*N.  Rank 0 prints one JSON line; the time is
 the max over ranks of K steps bracketed by barrier + device synchronize.
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, print the line.
+``--full`` adds what else the benchmark measures: the held-out accuracy of the model the timed steps produced
+(the metric's "event-cls accuracy" half; ``--heldout`` samples per GPU).  ``--dump-outputs DIR`` writes what
+the last timed step left its caller (``_dump_outputs``) as ``DIR/<name>.npy``; the data, the initial weights
+and the batch schedule are seeded, so two builds run with the same arguments can be compared array by array.
 
 Without a GPU (CPU container, tests) the same contract runs the reference-math fp32 PyTorch step over gloo
 (``_cpu_bench``): it checks the launch / rendezvous / one-JSON-line plumbing, not performance.
@@ -50,6 +56,24 @@ def _accs(m, joint):
     if joint:
         return {"distance": round(float(m[1, 1] / m[1, 2]), 4), "event": round(float(m[2, 1] / m[2, 2]), 4)}
     return {"distance": round(float(m[0, 1] / m[0, 2]), 4), "event": round(float(m[-1, 1] / m[-1, 2]), 4)}
+
+
+DUMP_MAX_ELEMS = 8 * 2 ** 20  # per array (32 MiB of float32): larger ones are sampled
+
+
+def _dump_outputs(path, arrays):
+    """Write ``arrays`` (name -> tensor) as ``path/<name>.npy`` in float32 (float64 stays float64).  An array of
+    more than DUMP_MAX_ELEMS elements is written as a fixed sample of its flattened elements: DUMP_MAX_ELEMS
+    sorted indices drawn without replacement from a generator seeded with 0, the same in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.size > DUMP_MAX_ELEMS:
+            pick = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _free_port() -> int:
@@ -108,9 +132,12 @@ def _cpu_bench(args, ctx):
     red = FlatGradAllReducer(ctx)
     g = torch.Generator().manual_seed(7 + ctx.rank)
 
+    last = {}
+
     def step():
         idx = torch.randint(0, n, (args.batch,), generator=g)
         out = model(X[idx])
+        last["out"] = out
         if joint:
             loss = F.cross_entropy(out[0] if isinstance(out, tuple) else out, encode_joint(d[idx], e[idx]))
         elif args.model == "MTL":
@@ -138,6 +165,11 @@ def _cpu_bench(args, ctx):
         step()
     ctx.barrier()
     dt = ctx.max_scalar(time.perf_counter() - t0)
+    if args.dump_outputs and ctx.is_main and "out" in last:
+        outs = last["out"] if isinstance(last["out"], tuple) else (last["out"],)
+        arrays = {f"out{i}": o for i, o in enumerate(outs)}
+        arrays["params"] = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+        _dump_outputs(args.dump_outputs, arrays)
     value = ctx.world * args.batch * args.steps / dt
     return {
         "metric": METRIC, "value": round(value, 2), "unit": "samples/s", "n_gpus": ctx.world, "steps": args.steps,
@@ -162,7 +194,13 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of one HIP graph per step")
     ap.add_argument("--buckets", type=int, default=None,
                     help="DP gradient buckets overlapped with the backward (default: the model's, 1 on one GPU)")
-    ap.add_argument("--heldout", type=int, default=1024, help="held-out samples per GPU evaluated after timing")
+    ap.add_argument("--heldout", type=int, default=1024,
+                    help="held-out samples per GPU evaluated after timing (with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the held-out evaluation after timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (log-probabilities of its batch, metrics, "
+                         "updated weights, BN running statistics) as DIR/<name>.npy")
     ap.add_argument("--no-tune", action="store_true", help="skip per-layer kernel autotuning (cached table only)")
     ap.add_argument("--in_channels", type=int, default=1,
                     help="input channels of the synthetic DAS matrices (reference 1; BASELINE north star 2)")
@@ -286,12 +324,17 @@ def main():
     ctx.barrier()
     dt = time.perf_counter() - t0
     dt = ctx.max_scalar(dt)
+    if args.dump_outputs and ctx.is_main:
+        # what the last timed step left its caller: the head's log-probabilities (Model C: logits) of its
+        # batch, the metrics accumulated over the timed steps, the updated weights and BN running statistics
+        _dump_outputs(args.dump_outputs, {"logp": prog.logp, "metrics": prog.metrics, "params": f.params,
+                                          "bn_mean": f.bn_mean, "bn_var": f.bn_var})
     m = prog.metrics.clone()
     ctx.all_reduce_(m)
     # after the timed region: held-out accuracy of the model the timed steps produced (the metric's
     # "event-cls accuracy" half) on samples no rank trained on, BN in eval mode (running statistics)
     mh = None
-    if args.heldout >= args.batch:
+    if args.full and args.heldout >= args.batch:
         Xh, dh, eh = generate(args.heldout, seed=500000 + ctx.rank, device=dev, in_channels=args.in_channels)
         runner.set_eval_source(Xh, encode_joint(dh, eh) if joint else torch.stack([dh, eh], 1))
         runner.reset_metrics()
@@ -321,7 +364,7 @@ def main():
         "heldout_acc_after_timed_steps": _accs(mh, joint) if mh is not None else None,
         "heldout_note": "held-out accuracy after only warmup + timed steps of training (near initialisation), "
                         "not a converged accuracy; converged numbers: docs/ACCURACY.md",
-        "heldout_samples": (args.heldout // args.batch) * args.batch * world,
+        "heldout_samples": (args.heldout // args.batch) * args.batch * world if mh is not None else 0,
         "train_steps_before_heldout": args.warmup + args.steps,
         "vs_eager_pytorch_mi355x": (round(value / (EAGER_BY_MODEL[args.model] * world), 3)
                                     if args.model in EAGER_BY_MODEL else None),
