@@ -189,7 +189,10 @@ struct HeadArgs {
   int64_t dgs;
   float* metrics;   // [T][4]: loss_sum, correct, count, abs_err_sum
   int* confusion;   // [T][16][16]
-  const int64_t* nvalid;  // samples b >= *nvalid are padding: no metrics, no gradient (may be null)
+  // samples b >= *nvalid are padding (may be null: none): they are left out of metrics and confusion only.
+  // logp and the gradient are written for all B rows, the gradient scaled by 1/B; training always runs with
+  // *nvalid == B
+  const int64_t* nvalid;
 };
 
 struct ClsArgs {
@@ -206,7 +209,10 @@ struct ClsArgs {
   float* metrics;                // [3][4]: joint, distance, event -> loss, correct, count, abs_err
   int* confusion;                // [2][16][16]: distance, event
   float* dW; float* db;          // flat-grad slots (cls_wgrad)
-  const int64_t* nvalid;         // padding mask for metrics (may be null)
+  // samples b >= *nvalid are padding (may be null: none): they are left out of metrics and confusion only.
+  // logits and the gradients are written for all B rows, the gradients scaled by 1/B; training always runs
+  // with *nvalid == B
+  const int64_t* nvalid;
 };
 
 // ------------------------------------------------------------------------------------------------

@@ -446,6 +446,72 @@ def test_bn_eval_mode(fn):
     out = fn.bn_tail(1, nhwc(y).bfloat16(), bn)
     ref = F.relu(F.batch_norm(y, rm, rv, gamma, beta, training=False))
     assert rel(nchw(out), ref) < 6e-3
+    # every tail kind, and ADD_RELU with a projection BN that is in eval mode too
+    for C in (16, 48):
+        for kind in range(6):
+            _bn_eval_case(fn, kind, C, False)
+        _bn_eval_case(fn, 4, C, True)
+
+
+def _eval_bn(fn, C, count, g):
+    """An eval-mode BN descriptor with zeroed batch-statistic replicas: only the running statistics can give
+    the right answer."""
+    gamma, beta = torch.rand(C, generator=g).cuda() + 0.5, torch.randn(C, generator=g).cuda()
+    rm, rv = torch.randn(C, generator=g).cuda(), torch.rand(C, generator=g).cuda() + 0.5
+    nbt = torch.full((1,), 3, device="cuda", dtype=torch.int64)
+    st = torch.zeros(NREP, 2, C, device="cuda", dtype=torch.float64)
+    return fn.bn_args(st, gamma, beta, rm, rv, nbt, count, training=False), gamma, beta, rm, rv, nbt
+
+
+def _bn_eval_case(fn, kind, C, proj):
+    g = torch.Generator().manual_seed(300 + 10 * kind + C + int(proj))
+    B, H, W = 2, 9, 21
+    y = (torch.randn(B, C, H, W, generator=g) * 2 + 0.5).bfloat16().float().cuda()
+    r = torch.randn(B, C, H, W, generator=g).bfloat16().float().cuda()
+    bn, gamma, beta, rm, rv, nbt = _eval_bn(fn, C, B * H * W, g)
+    state = [rm, rv, nbt]
+    z = F.batch_norm(y, rm, rv, gamma, beta, training=False)
+    bn2 = None
+    if proj:
+        bn2, gamma2, beta2, rm2, rv2, nbt2 = _eval_bn(fn, C, B * H * W, g)
+        state += [rm2, rv2, nbt2]
+        out = F.relu(z + F.batch_norm(r, rm2, rv2, gamma2, beta2, training=False))
+    elif kind == 0:
+        out = z
+    elif kind == 1:
+        out = F.relu(z)
+    elif kind == 2:
+        out = torch.sigmoid(z)
+    elif kind == 3:
+        out = torch.sigmoid(z) * r
+    elif kind == 4:
+        out = F.relu(z + r)
+    else:
+        out = F.max_pool2d(F.relu(z), 2, 2, ceil_mode=True)
+    before = [t.clone() for t in state]
+    ours = fn.bn_tail(kind, nhwc(y).bfloat16(), bn, r=nhwc(r).bfloat16() if kind in (3, 4) else None, bn2=bn2)
+    assert rel(nchw(ours), out) < 6e-3, (kind, C, proj)
+    for a, b in zip(state, before):  # eval leaves the running statistics and num_batches_tracked alone
+        assert torch.equal(a, b), (kind, C, proj)
+
+
+@pytest.mark.parametrize("kind", [0, 1])
+def test_conv_normalise_on_load_eval(fn, kind):
+    """Normalise-on-load in eval mode: the operand is act(BN(y)) with the running statistics, which (with
+    num_batches_tracked) stay as they were."""
+    B, H, W, C, Co, k, s, p = (4, 9, 21, 64, 128, 3, 2, 1)
+    g = torch.Generator().manual_seed(60 + kind)
+    y = (torch.randn(B, C, H, W, generator=g) * 2 + 0.3).bfloat16().float().cuda()
+    bn, gamma, beta, rm, rv, nbt = _eval_bn(fn, C, B * H * W, g)
+    before = [t.clone() for t in (rm, rv, nbt)]
+    w = (torch.randn(Co, C, k, k, generator=g) / math.sqrt(C * k * k)).bfloat16().float().cuda()
+    z = F.batch_norm(y, rm, rv, gamma, beta, training=False)
+    act = (z if kind == 0 else F.relu(z)).bfloat16().float()  # the engine's operand is bf16
+    ref = F.conv2d(act, w, stride=s, padding=p)
+    out = fn.conv2d(nhwc(y).bfloat16(), w, stride=s, padding=p, nol=(bn, kind), cfg=None)
+    assert rel(nchw(out), ref) < 6e-3
+    for a, b in zip((rm, rv, nbt), before):
+        assert torch.equal(a, b)
 
 
 @pytest.mark.parametrize("is_max", [True, False])
