@@ -2,7 +2,7 @@
 """Sliding-window inference over a long DAS recording (fiber x time matrix, .npy or .mat).
 
     python infer.py --model MTL --model_path run/<...>.pth --recording fiber.npy --stride 100,125 \
-        --out predictions.csv
+        --out predictions.csv --cell 50,125 --map maps.npz
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 infer.py ...   # windows sharded over ranks
 """
 import argparse
@@ -23,6 +23,8 @@ def main():
     ap.add_argument("--in_channels", type=int, default=1)
     ap.add_argument("--backend", choices=["auto", "engine", "torch"], default="auto")
     ap.add_argument("--out", default="predictions.csv")
+    ap.add_argument("--cell", default=None, help="map cell (fiber, time) in samples; default: the stride")
+    ap.add_argument("--map", default=None, help="write the event / distance maps of the recording to this .npz")
     args = ap.parse_args()
 
     from mtl_das_pytorch_amd import use_engine_graph_queues
@@ -30,10 +32,16 @@ def main():
     import numpy as np
     import torch
     from mtl_das_pytorch_amd.data.mat_dataset import load_mat
-    from mtl_das_pytorch_amd.inference import predict_recording
+    from mtl_das_pytorch_amd.inference import WINDOW, predict_recording, prediction_map, window_starts
     from mtl_das_pytorch_amd.models import build_model
     from mtl_das_pytorch_amd.parallel.dist import init_distributed, shutdown
 
+    stride = tuple(int(s) for s in args.stride.split(","))
+    cell = tuple(int(s) for s in args.cell.split(",")) if args.cell else stride
+    if args.map and (stride[0] > WINDOW[0] or stride[1] > WINDOW[1] or min(cell) < 1):
+        # checked before the run, not after it: with a stride past the window some samples are in no window
+        ap.error(f"--map needs windows that cover the recording: --stride at most {WINDOW[0]},{WINDOW[1]} "
+                 "and a positive --cell")
     ctx = init_distributed()
     model = build_model(args.model, in_channels=args.in_channels)
     if args.model_path:
@@ -43,8 +51,8 @@ def main():
     else:
         rec = np.load(args.recording, allow_pickle=False).astype(np.float32)
     use_engine = {"auto": None, "engine": True, "torch": False}[args.backend]
-    res = predict_recording(model, args.model, torch.from_numpy(rec), stride=tuple(int(s) for s in args.stride.split(",")),
-                            batch=args.batch_size, ctx=ctx, use_engine=use_engine)
+    res = predict_recording(model, args.model, torch.from_numpy(rec), stride=stride, batch=args.batch_size, ctx=ctx,
+                            use_engine=use_engine)
     if ctx.is_main:
         import pandas as pd
         cols = {"fiber_start": res["positions"][:, 0], "time_start": res["positions"][:, 1]}
@@ -53,6 +61,18 @@ def main():
                 cols[k] = res[k]
         pd.DataFrame(cols).to_csv(args.out, index=False)
         print(f"{len(res['positions'])} windows -> {args.out}")
+        if args.map:
+            shape = rec.shape[-2:]
+            fs, ts = window_starts(shape[0], WINDOW[0], stride[0]), window_starts(shape[1], WINDOW[1], stride[1])
+            probs = res["joint_prob"] if "joint_prob" in res else np.concatenate(
+                [res[k] for k in ("distance_prob", "event_prob") if k in res], 1)
+            if ctx.device.type == "cuda" and use_engine is not False:  # summed on the device; numpy fp64 otherwise
+                probs = torch.from_numpy(probs).to(ctx.device)
+            maps = prediction_map(probs, fs, ts, shape, cell)
+            nfc, ntc = next(iter(maps.values())).shape[-2:]
+            np.savez(args.map, fiber_edges=np.minimum(np.arange(nfc + 1) * cell[0], shape[0]),
+                     time_edges=np.minimum(np.arange(ntc + 1) * cell[1], shape[1]), **maps)
+            print(f"{nfc} x {ntc} cells -> {args.map}")
     shutdown(ctx)
 
 

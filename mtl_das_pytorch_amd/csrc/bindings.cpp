@@ -348,6 +348,42 @@ void gather_batch(int64_t X, int64_t idx, int64_t lab, int lab_w, int64_t out, i
         "gather_batch");
 }
 
+WindowArgs parse_window(const py::dict& d) {
+  WindowArgs a{};
+  a.rec = P<const float>(d, "rec"); a.fs = P<const int>(d, "fs"); a.ts = P<const int>(d, "ts");
+  a.C = (int)I(d, "C"); a.F = (int)I(d, "F"); a.T = (int)I(d, "T"); a.nf = (int)I(d, "nf"); a.nt = (int)I(d, "nt");
+  a.B = (int)I(d, "B"); a.Wf = (int)I(d, "Wf"); a.Wt = (int)I(d, "Wt");
+  a.taps = (int)I(d, "taps"); a.off = (int)I(d, "off");
+  a.idx = P<const int64_t>(d, "idx"); a.cursor = P<int64_t>(d, "cursor");
+  a.lo = I(d, "lo"); a.hi = I(d, "hi");
+  return a;
+}
+
+void gather_windows(int64_t stream, py::dict d) {
+  check(launch_gather_windows(parse_window(d), P<bf16_t>(d, "out"), P<int64_t>(d, "lab_out"), (int)I(d, "lab_w"),
+                              S(stream)), "gather_windows");
+}
+
+void window_probs(int64_t stream, py::dict d) {
+  std::vector<int> ncls;
+  if (d.contains("ncls")) ncls = d["ncls"].cast<std::vector<int>>();
+  if (ncls.size() > 4) throw std::runtime_error("window_probs: at most 4 tasks");
+  check(launch_window_probs(parse_window(d), P<const float>(d, "src"), (int)I(d, "softmax"), (int)ncls.size(),
+                            ncls.data(), (int)I(d, "K"), P<float>(d, "probs"), I(d, "nprobs"), S(stream)),
+        "window_probs");
+}
+
+void window_map(int64_t stream, py::dict d, std::vector<int> fs, std::vector<int> ts) {
+  MapArgs a{};
+  a.probs = P<const float>(d, "probs"); a.fs = P<const int>(d, "fs"); a.ts = P<const int>(d, "ts");
+  a.map = P<float>(d, "map");
+  a.wf = P<const float>(d, "wf"); a.wt = P<const float>(d, "wt"); a.mf = (int)I(d, "mf"); a.mt = (int)I(d, "mt");
+  a.nf = (int)fs.size(); a.nt = (int)ts.size(); a.K = (int)I(d, "K"); a.F = (int)I(d, "F"); a.T = (int)I(d, "T");
+  a.Wf = (int)I(d, "Wf"); a.Wt = (int)I(d, "Wt"); a.cf = (int)I(d, "cf"); a.ct = (int)I(d, "ct");
+  a.nfc = (int)I(d, "nfc"); a.ntc = (int)I(d, "ntc");
+  check(launch_window_map(a, fs.data(), ts.data(), S(stream)), "window_map");
+}
+
 void pool3(int is_max, int backward, int64_t stream, py::dict d) {
   PoolArgs a{};
   a.x = P<const bf16_t>(d, "x"); a.ldx = (int)I(d, "ldx");
@@ -441,6 +477,9 @@ PYBIND11_MODULE(_mda_hip, m) {
         py::arg("taps") = 0, py::arg("off") = 0, py::arg("zero") = py::list(), py::arg("cursor") = 0,
         py::arg("nrows") = 0);
   m.def("pool3", &pool3);
+  m.def("gather_windows", &gather_windows);
+  m.def("window_probs", &window_probs);
+  m.def("window_map", &window_map, py::arg("stream"), py::arg("d"), py::arg("fs"), py::arg("ts"));
   m.def("wgrad_table", &wgrad_table);
   m.def("wgrad_batched", &wgrad_batched, py::arg("cfg"), py::arg("table"), py::arg("nj"), py::arg("nblocks"),
         py::arg("stream"), py::arg("cap") = 0);

@@ -311,6 +311,39 @@ int launch_gather_batch(const float* X, const int64_t* idx, const int64_t* lab, 
                         const int64_t* cursor, int nrows,
                         hipStream_t st);
 int launch_pool3(int is_max, int backward, const PoolArgs& a, hipStream_t st);
+// window.hip: resident-recording inference -- windows cut on the device, probabilities into a resident table,
+// overlapping windows averaged into a cell map
+struct WindowArgs {
+  const float* rec;   // recording [C][F][T] fp32 (gather_windows only)
+  const int* fs;      // window starts along the fiber [nf] and along time [nt]; window n = a * nt + b
+  const int* ts;
+  int C, F, T, nf, nt;
+  int B, Wf, Wt;      // batch rows, window size
+  int taps, off;      // vertical tap packing of a 1-channel stem (gather_batch)
+  // batch row r holds window idx[r], or lo + *cursor * B + r (exactly one of idx / cursor is set); a row whose
+  // window number is outside [lo, hi) is padding: gathered as zeros, skipped by window_probs
+  const int64_t* idx;
+  int64_t* cursor;    // advanced by window_probs
+  int64_t lo, hi;
+};
+int launch_gather_windows(const WindowArgs& a, bf16_t* out, int64_t* lab_out, int lab_w, hipStream_t st);
+// softmax = 0: src = logp [T][B][16], ncls[t] columns per task side by side (their sum is K); 1: src = logits [B][K]
+int launch_window_probs(const WindowArgs& a, const float* src, int softmax, int T, const int* ncls, int K,
+                        float* probs, int64_t nprobs, hipStream_t st);
+struct MapArgs {
+  const float* probs;  // [nf * nt][K]
+  const int* fs;       // device copies of the start tables
+  const int* ts;
+  float* map;          // [K][nfc][ntc]
+  // per-axis weights of a window in the cells it reaches, as bands (window.hip window_map_kernel): wf [nf][mf] from
+  // cell row fs[a] / cf on, wt [nt][mt] from cell column ts[b] / ct on; mf = (Wf - 1) / cf + 2, mt likewise
+  const float* wf;
+  const float* wt;
+  int mf, mt;
+  int nf, nt, K, F, T, Wf, Wt, cf, ct, nfc, ntc;
+};
+// h_fs / h_ts: host copies of the start tables, checked to cover [0, F) x [0, T) (-2 otherwise)
+int launch_window_map(const MapArgs& a, const int* h_fs, const int* h_ts, hipStream_t st);
 // synth.hip: on-device synthetic DAS samples (data/synthetic.py physical model, Philox noise)
 constexpr int SYNTH_NPARAM = 9;  // per sample: distance, event, x0, t0, jitter[4], snr_db
 struct SynthArgs {

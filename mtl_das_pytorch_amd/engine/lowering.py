@@ -12,9 +12,9 @@ from ..ops.functional import WGRAD_PATCH, WGRAD_TILES, wgrad_ktiles
 from ..ops.hip import lib
 from .core import (GRAD_DT, Act, BNLayer, ConvLayer, P, build_optseg_table, build_wgfin_table, optimizer_segments,
                    pad_to)
-from .program import (COMM_STREAM, SPILL_STREAM, Launch, Phase, k_adam, k_step_inc, k_allreduce, k_ext_record, k_conv, k_gather, k_tail_bwd, k_tail_fwd,
+from .program import (COMM_STREAM, SPILL_STREAM, Launch, Phase, k_adam, k_step_inc, k_allreduce, k_ext_record, k_conv, k_gather, k_gather_windows, k_tail_bwd, k_tail_fwd,
                       k_tail_fwd_batched, k_wgfin, k_wgrad,
-                      k_wgrad_batched)
+                      k_wgrad_batched, k_window_probs)
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID, SIGMUL, ADD_RELU, POOL_RELU = range(6)
 
@@ -388,6 +388,64 @@ class LoweredProgram:
                 zero = []
         ph.add("gather", k_gather, X, idx, labels, self.label_width, self.x, self.labels, self.B, X.shape[1], self.H0,
                self.W0, *self.stem_pack, zero, cursor)
+        return ph
+
+    def _window_args(self, idx, cursor, lo: int, hi: int) -> dict:
+        if (idx is None) == (cursor is None):
+            raise ValueError("exactly one of idx / cursor")
+        for t in (idx, cursor):
+            if t is not None and (t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("window numbers / cursor must be contiguous int64 tensors on the device")
+        if idx is not None and idx.numel() != self.B:
+            raise ValueError(f"idx must hold {self.B} window numbers")
+        return {"B": self.B, "idx": P(idx), "cursor": P(cursor), "lo": int(lo), "hi": int(hi)}
+
+    def window_gather_phase(self, rec, fs, ts, idx=None, cursor=None, lo: int = 0, hi: Optional[int] = None) -> Phase:
+        """The batch gather of resident-recording inference: the batch's (H0, W0) windows are cut from ``rec``
+        ([C, F, T] fp32 on the device) into the stem's input, labels zeroed.  ``fs`` / ``ts``: int32 device
+        tables of the window starts, window ``n = a * len(ts) + b``; batch row ``r`` is window ``idx[r]`` or
+        ``lo + cursor * B + r`` (``cursor``: a device int64 scalar that window_probs_phase advances); rows whose
+        window number is outside ``[lo, hi)`` are zeros."""
+        if rec.dim() != 3 or rec.dtype != torch.float32 or not rec.is_contiguous() or not rec.is_cuda:
+            raise ValueError("recording must be a contiguous fp32 [C, F, T] tensor on the device")
+        if self.stem_pack[0] and rec.shape[0] != 1:
+            raise ValueError("stem tap packing needs a single-channel input")
+        for t in (fs, ts):
+            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("window-start tables must be contiguous int32 vectors on the device")
+        d = self._window_args(idx, cursor, lo, fs.numel() * ts.numel() if hi is None else hi)
+        d.update({"rec": P(rec), "fs": P(fs), "ts": P(ts), "C": rec.shape[0], "F": rec.shape[1], "T": rec.shape[2],
+                  "nf": fs.numel(), "nt": ts.numel(), "Wf": self.H0, "Wt": self.W0, "taps": self.stem_pack[0],
+                  "off": self.stem_pack[1], "out": P(self.x), "lab_out": P(self.labels), "lab_w": self.label_width})
+        ph = Phase("window_gather")
+        ph.add("gather_windows", k_gather_windows, d)
+        ph.keep = (rec, fs, ts, idx, cursor)  # the launch holds their device pointers
+        return ph
+
+    def prob_classes(self) -> List[int]:
+        """Columns of the per-window probability table, the tasks side by side: 16 distance bins and / or 2 event
+        types for the task heads (logp [T, B, 16]), the joint classes for Model C (logits [B, N])."""
+        if self.logp.dim() == 2:
+            return [self.logp.shape[1]]
+        return [16 if o == 0 else 2 for o in self.lab_off]
+
+    def window_probs_phase(self, probs, idx=None, cursor=None, lo: int = 0, hi: Optional[int] = None) -> Phase:
+        """After ``fwd_eval``: the batch's probabilities into rows of the resident table ``probs`` [N, K] (fp32) --
+        ``exp`` of the heads' log-probabilities, or the softmax of Model C's logits -- for the batch rows whose
+        window number is in ``[lo, hi)``; in cursor form the launch then advances the cursor by one."""
+        ncls = self.prob_classes()
+        if (probs.dtype != torch.float32 or probs.dim() != 2 or not probs.is_contiguous() or not probs.is_cuda
+                or probs.shape[1] != sum(ncls)):
+            raise ValueError(f"probability table must be a contiguous fp32 [N, {sum(ncls)}] tensor on the device")
+        d = self._window_args(idx, cursor, lo, probs.shape[0] if hi is None else hi)
+        softmax = self.logp.dim() == 2
+        d.update({"src": P(self.logp), "softmax": int(softmax), "K": probs.shape[1], "probs": P(probs),
+                  "nprobs": probs.shape[0]})
+        if not softmax:
+            d["ncls"] = ncls
+        ph = Phase("window_probs")
+        ph.add("window_probs", k_window_probs, d)
+        ph.keep = (probs, idx, cursor)
         return ph
 
     def _wgfin_args(self, convs=None):

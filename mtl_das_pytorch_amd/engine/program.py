@@ -339,3 +339,13 @@ def k_gather(X, idx, lab, lab_w, out, lab_out, B, Cin, H, W, taps, off, zero, cu
     lib().gather_batch(X.data_ptr(), idx.data_ptr(), lab.data_ptr(), lab_w, out.data_ptr(), lab_out.data_ptr(),
                        B, Cin, H, W, st, taps, off, zero, cursor.data_ptr() if cursor is not None else 0,
                        idx.shape[0] if cursor is not None else 0)
+
+
+def k_gather_windows(d, st):
+    """The batch's windows cut from a resident recording (csrc/window.hip; ``d``: the launch's argument dict)."""
+    lib().gather_windows(st, d)
+
+
+def k_window_probs(d, st):
+    """The batch's probabilities into the resident table; in cursor form it advances the batch cursor."""
+    lib().window_probs(st, d)

@@ -18,6 +18,13 @@ the graph computes the rest of the backward; the optimizer graph waits for every
 The batch indices come from a device-resident schedule (set_index_schedule: the gather reads the next row,
 the optimizer kernel advances the cursor) or from a persistent device buffer the host refreshes before each
 replay; the learning rate is a device scalar, so the reference's LR schedule never forces a re-capture.
+
+An inference step over a resident recording (set_window_source / infer_step) is
+
+    [window gather from the recording] [eval forward] [probabilities -> resident table, batch cursor++]
+
+one graph too: the batch's windows are numbered by a device cursor that the step's last kernel advances, so the
+replays that cover a recording need no host copy between them.
 """
 from __future__ import annotations
 
@@ -91,6 +98,9 @@ class StepRunner:
         self.buckets = list(getattr(program, "buckets", None) or [(0, program.flat.numel)])
         self.schedule = None  # [nrows][B] batch-index schedule (set_index_schedule)
         self.cursor = None
+        self.window = None  # resident-recording inference (set_window_source): (rec, fs, ts, probs, lo, hi)
+        self.window_cursor = None
+        self.window_key = None  # what the source's owner knows it by (inference.resident_probs: shape and starts)
 
     def set_index_schedule(self, schedule: Optional[torch.Tensor]):
         """Train from a device-resident [nrows][B] batch-index schedule: ``train_step()`` without indices then
@@ -118,11 +128,14 @@ class StepRunner:
         self.cursor.zero_()
 
     # -------------------------------------------------------------------------------------------
-    def _mutable_state(self) -> List[torch.Tensor]:
+    def _mutable_state(self, kind: Optional[str] = None) -> List[torch.Tensor]:
         f = self.p.flat
+        # the inference step advances its batch cursor and fills rows of the probability table: a warm-up that
+        # left either behind would skip the first batch
+        infer = [self.window_cursor, self.window[3]] if kind == "infer" else []
         return ([f.params, f.grads, f.exp_avg, f.exp_avg_sq, f.bn_mean, f.bn_var, f.bn_nbt, f.step, self.p.metrics,
                  self.p.confusion, self.p.logp] + list(getattr(self.p, "extra_state", []))
-                + ([self.cursor] if self.cursor is not None else []))
+                + ([self.cursor] if self.cursor is not None else []) + infer)
 
     def pack_weights(self):
         """(Re)build the bf16 MFMA weight images from the fp32 masters (after init / load_state_dict)."""
@@ -131,6 +144,11 @@ class StepRunner:
 
     def _phases(self, kind: str) -> List[Callable[[], None]]:
         p = self.p
+        if kind == "infer":
+            rec, fs, ts, probs, lo, hi = self.window
+            gather = p.window_gather_phase(rec, fs, ts, cursor=self.window_cursor, lo=lo, hi=hi)
+            store = p.window_probs_phase(probs, cursor=self.window_cursor, lo=lo, hi=hi)
+            return [gather.run, p.fwd_eval.run, store.run]
         X, lab = self.sources["train" if kind.startswith("train") else "eval"]
         # a training step's gather also zeroes the arena's accumulators (one launch; arena.clear otherwise)
         sched = self.schedule is not None and kind.startswith("train")
@@ -178,7 +196,7 @@ class StepRunner:
         g = self.graphs.get(kind)
         if g is None:
             fns = self._phases(kind)
-            snap = StateSnapshot(self._mutable_state())
+            snap = StateSnapshot(self._mutable_state(kind))
             s = EngineStreams.get(torch.cuda.current_stream().device).capture
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):  # warm-up (loads code objects); side effects are rolled back
@@ -252,6 +270,43 @@ class StepRunner:
             self.pack_weights()
         self.idx.copy_(idx, non_blocking=True)
         self._run("eval")
+
+    def set_window_source(self, rec: torch.Tensor, fs: torch.Tensor, ts: torch.Tensor, probs: torch.Tensor,
+                          lo: int = 0, hi: Optional[int] = None, key=None):
+        """Resident-recording inference: ``infer_step()`` then evaluates the next ``B`` windows of ``[lo, hi)`` --
+        cut on the device from ``rec`` [C, F, T] at the starts ``fs`` x ``ts`` (int32 device tables, window
+        ``n = a * len(ts) + b``) -- and writes their probabilities into rows of ``probs`` [N, K]; the step's last
+        kernel advances the batch cursor, so ceil((hi - lo) / B) calls cover the range with no host copy between
+        them.  The cursor restarts at ``lo``.  Other tensors or another range rebuild the captured graph (its
+        launches hold the device pointers and the range).  ``key``: kept as ``window_key`` until the source is
+        replaced or cleared -- how a caller that uploaded the tensors recognises them again."""
+        hi = fs.numel() * ts.numel() if hi is None else hi
+        if probs.shape[0] != fs.numel() * ts.numel():
+            raise ValueError("the probability table needs one row per window")
+        if not 0 <= lo <= hi <= probs.shape[0]:
+            raise ValueError(f"window range [{lo}, {hi}) outside the {probs.shape[0]} windows")
+        if self.window_cursor is None:
+            self.window_cursor = torch.zeros(1, dtype=torch.int64, device=self.p.device)
+        cur = self.window
+        new = (rec, fs, ts, probs, int(lo), int(hi))
+        if cur is None or any(a is not b for a, b in zip(cur[:4], new[:4])) or cur[4:] != new[4:]:
+            self.window = new
+            self._drop_graph("infer")
+        self.window_key = key
+        self.window_cursor.zero_()
+
+    def clear_window_source(self):
+        """Release the window source (the recording and its table can be freed before the next one is uploaded)."""
+        self._drop_graph("infer")
+        self.window = self.window_key = None
+
+    def infer_step(self):
+        """One batch of the window source: [window gather, eval forward, probabilities + cursor], one graph."""
+        if self.window is None:
+            raise ValueError("infer_step() needs set_window_source")
+        if not self._packed:
+            self.pack_weights()
+        self._run("infer")
 
     def reset_metrics(self):
         self.p.metrics.zero_()

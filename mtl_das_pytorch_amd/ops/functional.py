@@ -465,3 +465,129 @@ def gather_batch(X: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor):
     lab = torch.empty(B, lw, device=X.device, dtype=torch.int64)
     lib().gather_batch(ptr(X), ptr(idx), ptr(labels), lw, ptr(out), ptr(lab), B, Cin, H, W, stream())
     return out, lab
+
+
+def _starts(s, device) -> torch.Tensor:
+    """A window-start table as the kernels read it: int32 on the device."""
+    return torch.as_tensor(s).to(device=device, dtype=torch.int32).contiguous()
+
+
+def gather_windows(rec: torch.Tensor, fs, ts, window: Tuple[int, int], B: int, idx: Optional[torch.Tensor] = None,
+                   cursor: Optional[torch.Tensor] = None, lo: int = 0, hi: Optional[int] = None, taps: int = 0,
+                   off: int = 0, lab_w: int = 2):
+    """Windows of an HBM-resident recording ``rec`` [C, F, T] (fp32) -> (bf16 NHWC batch with C padded to 8, zero
+    labels), the layout of :func:`gather_batch` of the materialised windows.  Window ``n = a * len(ts) + b`` starts
+    at ``(fs[a], ts[b])``; batch row ``r`` holds window ``idx[r]`` (int64 [B]) or ``lo + cursor * B + r`` (``cursor``:
+    a device int64 scalar).  Rows whose window number is outside ``[lo, hi)`` are zeros.  ``taps`` / ``off``: the
+    1-channel stem's vertical tap packing, padded at the window's edges."""
+    _check(rec, torch.float32)
+    if rec.dim() != 3:
+        raise ValueError("recording must be [C, F, T]")
+    if (idx is None) == (cursor is None):
+        raise ValueError("exactly one of idx / cursor")
+    C, Fn, Tn = rec.shape
+    fs, ts = _starts(fs, rec.device), _starts(ts, rec.device)
+    for t in (idx, cursor):
+        if t is not None:
+            _check(t, torch.int64)
+    if idx is not None and idx.numel() != B:
+        raise ValueError("idx must hold B window numbers")
+    hi = fs.numel() * ts.numel() if hi is None else hi
+    out = torch.empty(B, window[0], window[1], 8, device=rec.device, dtype=torch.bfloat16)
+    lab = torch.empty(B, lab_w, device=rec.device, dtype=torch.int64)
+    lib().gather_windows(stream(), {"rec": ptr(rec), "fs": ptr(fs), "ts": ptr(ts), "C": C, "F": Fn, "T": Tn,
+                                    "nf": fs.numel(), "nt": ts.numel(), "B": B, "Wf": window[0], "Wt": window[1],
+                                    "taps": taps, "off": off, "idx": ptr(idx), "cursor": ptr(cursor), "lo": lo,
+                                    "hi": hi, "out": ptr(out), "lab_out": ptr(lab), "lab_w": lab_w})
+    return out, lab
+
+
+def window_probs(src: torch.Tensor, probs: torch.Tensor, idx: Optional[torch.Tensor] = None,
+                 cursor: Optional[torch.Tensor] = None, lo: int = 0, hi: Optional[int] = None,
+                 ncls: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """The batch's class probabilities into the resident table ``probs`` [N, K] (fp32, in place): row ``r`` of the
+    batch goes to row ``idx[r]`` / ``lo + cursor * B + r``; rows outside ``[lo, hi)`` are skipped.  ``ncls`` given
+    (Models A/B): ``src`` is the heads' log-probabilities [T, B, 16] and the table holds ``exp`` of the first
+    ``ncls[t]`` columns of every task side by side.  Otherwise (Model C) ``src`` is logits [B, K] and the table holds
+    their softmax.  In cursor form the launch advances the cursor by one."""
+    _check(src, torch.float32)
+    _check(probs, torch.float32)
+    if (idx is None) == (cursor is None):
+        raise ValueError("exactly one of idx / cursor")
+    for t in (idx, cursor):
+        if t is not None:
+            _check(t, torch.int64)
+    N, K = probs.shape
+    if ncls is not None:
+        if src.dim() != 3 or src.shape[2] != 16 or src.shape[0] != len(ncls):
+            raise ValueError("log-probabilities must be [T, B, 16] with one ncls per task")
+        B = src.shape[1]
+    else:
+        if src.dim() != 2 or src.shape[1] != K:
+            raise ValueError("logits must be [B, K]")
+        B = src.shape[0]
+    if idx is not None and idx.numel() != B:
+        raise ValueError("idx must hold B window numbers")
+    d = {"B": B, "idx": ptr(idx), "cursor": ptr(cursor), "lo": lo, "hi": N if hi is None else hi, "src": ptr(src),
+         "softmax": int(ncls is None), "K": K, "probs": ptr(probs), "nprobs": N}
+    if ncls is not None:
+        d["ncls"] = [int(k) for k in ncls]
+    lib().window_probs(stream(), d)
+    return probs
+
+
+def window_cell_weights(starts, win: int, length: int, cell: int):
+    """fp64 [windows, cells]: the weight of window ``a`` in cell ``i`` of one axis, when a sample's value is the
+    mean of the windows covering it and a cell's value the mean of its samples -- the sum over the samples the
+    window shares with the cell of 1 / (windows covering the sample), over the cell's size.  A cell's weights sum
+    to 1.  Raises if a sample of ``[0, length)`` is in no window."""
+    import numpy as np
+    s = np.asarray(starts, dtype=np.int64)
+    if s.ndim != 1 or len(s) < 1 or (s < 0).any() or (s + win > length).any():
+        raise ValueError("window starts outside the recording")
+    cover = np.zeros(length + 1)
+    np.add.at(cover, s, 1)
+    np.add.at(cover, s + win, -1)
+    cover = np.cumsum(cover)[:length]
+    if (cover <= 0).any():
+        raise ValueError("the window starts do not cover the recording")
+    ncell = -(-length // cell)
+    csum = np.concatenate([[0.0], np.cumsum(1.0 / cover)])  # csum[x] = sum of 1 / cover over [0, x)
+    c0 = np.arange(ncell, dtype=np.int64) * cell
+    c1 = np.minimum(c0 + cell, length)
+    lo = np.maximum(s[:, None], c0[None])
+    hi = np.maximum(np.minimum(s[:, None] + win, c1[None]), lo)
+    return (csum[hi] - csum[lo]) / (c1 - c0)[None]
+
+
+def _weight_band(w, starts, win: int, cell: int, device) -> torch.Tensor:
+    """The nonzero band of :func:`window_cell_weights` as the kernel reads it: fp32 [windows, (win - 1) // cell + 2],
+    window ``a``'s cells from ``starts[a] // cell`` on."""
+    import numpy as np
+    m = (win - 1) // cell + 2
+    j = np.asarray(starts, dtype=np.int64)[:, None] // cell + np.arange(m)[None]
+    band = np.where(j < w.shape[1], np.take_along_axis(w, np.minimum(j, w.shape[1] - 1), 1), 0.0)
+    return torch.from_numpy(band.astype(np.float32)).to(device).contiguous()
+
+
+def window_map(probs: torch.Tensor, fs, ts, shape: Tuple[int, int], window: Tuple[int, int],
+               cell: Tuple[int, int]) -> torch.Tensor:
+    """Per-window probabilities [len(fs) * len(ts), K] -> cell map [K, ceil(F / cf), ceil(T / ct)] (fp32): a
+    sample's value is the mean of the windows that cover it, a cell's value the mean of its samples.
+    ``fs`` / ``ts``: host window-start tables that cover ``shape`` = (F, T) (inference.window_starts); the per-axis
+    weights (:func:`window_cell_weights`) are computed on the host in fp64, the sums run on the device."""
+    _check(probs, torch.float32)
+    fs_h, ts_h = [int(v) for v in fs], [int(v) for v in ts]
+    N, K = probs.shape
+    if N != len(fs_h) * len(ts_h):
+        raise ValueError("probs must have one row per window")
+    nfc, ntc = -(-shape[0] // cell[0]), -(-shape[1] // cell[1])
+    fs_d, ts_d = _starts(fs_h, probs.device), _starts(ts_h, probs.device)
+    wf = _weight_band(window_cell_weights(fs_h, window[0], shape[0], cell[0]), fs_h, window[0], cell[0], probs.device)
+    wt = _weight_band(window_cell_weights(ts_h, window[1], shape[1], cell[1]), ts_h, window[1], cell[1], probs.device)
+    out = torch.empty(K, nfc, ntc, device=probs.device, dtype=torch.float32)
+    lib().window_map(stream(), {"probs": ptr(probs), "fs": ptr(fs_d), "ts": ptr(ts_d), "map": ptr(out), "K": K,
+                                "F": shape[0], "T": shape[1], "Wf": window[0], "Wt": window[1], "cf": cell[0],
+                                "ct": cell[1], "nfc": nfc, "ntc": ntc, "wf": ptr(wf), "wt": ptr(wt),
+                                "mf": wf.shape[1], "mt": wt.shape[1]}, fs_h, ts_h)
+    return out
