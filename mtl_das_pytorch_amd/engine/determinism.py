@@ -19,7 +19,7 @@ def check_step(prog, X: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor, u
     from .step import StepRunner
     f = prog.flat
     state = [f.params, f.exp_avg, f.exp_avg_sq, f.bn_mean, f.bn_var, f.bn_nbt, f.step] + \
-        list(getattr(prog, "extra_state", []))  # e.g. Model C's dropout RNG counter
+        list(prog.extra_state)  # e.g. Model C's dropout RNG counter
     saved = [t.clone() for t in state]
     grads, outs = [], []
     for _ in range(runs):
@@ -101,7 +101,7 @@ def first_divergent_launch(prog, X: torch.Tensor, labels: torch.Tensor, idx: tor
 
     launches = [(ph.name, i, l) for ph in (prog.fwd_train, prog.bwd) for i, l in enumerate(ph.launches)]
     state = [f.params, f.exp_avg, f.exp_avg_sq, f.bn_mean, f.bn_var, f.bn_nbt, f.step] + \
-        list(getattr(prog, "extra_state", []))
+        list(prog.extra_state)
     saved = [t.clone() for t in state]
 
     def execute():
@@ -117,7 +117,7 @@ def first_divergent_launch(prog, X: torch.Tensor, labels: torch.Tensor, idx: tor
                 continue
             l(st)
             torch.cuda.synchronize()
-            d = next((a for a in l.args if isinstance(a, dict)), {})
+            d = l.d or {}
             out = []
             for k in _OUT_KEYS:
                 v = d.get(k)
@@ -125,7 +125,7 @@ def first_divergent_launch(prog, X: torch.Tensor, labels: torch.Tensor, idx: tor
                 if r is not None:
                     base, nb, t = r
                     out.append((k, torch.empty(0, dtype=torch.uint8, device=t.device).set_(t.untyped_storage()).clone()))
-            if l.name == "wgrad_finalize":
+            if l.is_finalize:
                 out.append(("grads", f.grads.clone()))
             snaps.append(out)
         return snaps

@@ -30,7 +30,8 @@ from .core import (GRAD_DT, NREP, Act, Arena, BNLayer, ConvLayer, FlatState, P, 
                    src_dict, stem_pack_geom)
 from .lowering import ACT_RELU, LoweredProgram
 from ..ops.hip import lib
-from .program import Phase, k_allreduce, k_cls_head, k_pool, k_wgfin
+from .program import (Launch, Phase, k_allreduce, k_cls_head, k_pool, k_tail_bwd_batched, k_tail_fwd_batched,
+                      k_wgfin)
 
 
 class Val:
@@ -200,8 +201,7 @@ class InceptionProgram(LoweredProgram):
     # the step counter stays after the last Adam launch here: on the forward's first side stream it cost Model C
     # 0.7 % (9,567 / 9,566 vs 9,629 / 9,634 samples/s, interleaved; Model A +0.3 %, docs/PERF.md round 6)
     EARLY_STEP_COUNTER = False
-    # module order puts the stem (stream 0) first: build_for_stream_buckets rebuilds with stream_param_order
-    REORDER_FOR_STREAM_BUCKETS = True
+    REORDER_FOR_STREAM_BUCKETS = True  # module order puts the stem (stream 0) first
 
     def __init__(self, model: Multi_Classifier, batch: int, device, in_hw=(100, 250), p_drop: float = 0.5,
                  sync_world: int = 1, param_order=None):
@@ -221,6 +221,16 @@ class InceptionProgram(LoweredProgram):
             raise NotImplementedError("transform_input is not lowered")
         if model.num_classes > 64:
             raise ValueError("the fused classifier head supports at most 64 classes")
+        super().__init__()
+        # lowering state of this class, next to the base class's
+        self._block_fork = {}          # (phase name, block index) -> the block's fork point (_emit_streamed)
+        self._pending_tails: List[tuple] = []  # a block's deferred branch-output tails while it is emitted
+        self.n_nol = self.n_tail_batched = self.n_tail_bwd_batched = 0
+        self._stat_groups, self._part_groups = [], {}  # coalesced SyncBN replica rows (_plan_tail_batches)
+        self._sync_part_groups = {}    # enable_sync_bn: fork name -> the block's coalesced partial sums
+        self._sync_bwd_pending = set()  # blocks whose backward collective batch_tails must still insert
+        self._sync_allreduce = None
+        self._table = None             # the shipped config table (_patch_forward)
         self.model = model
         self.B = batch
         self.device = torch.device(device)
@@ -419,8 +429,6 @@ class InceptionProgram(LoweredProgram):
         """The BN+ReLU tails of an Inception block's branch outputs -- channel slices of the block's concat
         buffer, read only by the next block -- run as ONE launch after the block's branches join
         (_emit_streamed) instead of one per branch at the end of each branch stream."""
-        self._pending_tails: List[tuple] = []
-        self.n_tail_batched = 0
         if not self.tail_batch_enabled():
             return
         by_block: Dict[int, List[CBR]] = {}
@@ -434,7 +442,6 @@ class InceptionProgram(LoweredProgram):
         # backward: the batched reduce): their replica rows share one buffer each way, so SyncBN all-reduces
         # them with ONE collective per block and direction (enable_sync_bn, batch_tails).  Members of a
         # horizontally fused conv keep the fused conv's forward rows (reduced when that conv ran).
-        self._stat_groups, self._part_groups = [], {}
         for blk, ops in by_block.items():
             own = [op.bn for op in ops if op.fused is None]
             if len(own) >= 2:
@@ -450,8 +457,7 @@ class InceptionProgram(LoweredProgram):
         the head of every branch stream (csrc/bn.hip bnb_batched_kernel).  Each branch's first remaining
         launch waits for the batch.  Runs after the autotuner (which picks the per-tail variants the batch
         replaces); not with SyncBN (its collectives sit between the passes).  Returns the tails batched."""
-        from .program import Launch, k_tail_bwd_batched
-        sync = getattr(self, "sync_bn_world", None) is not None
+        sync = self.sync_bn_world is not None
         if not self.tail_batch_enabled():
             return 0
         ls = self.bwd.launches
@@ -463,17 +469,15 @@ class InceptionProgram(LoweredProgram):
         inserts = []
         for blk, tails in groups.items():
             cgb = 8
-            while any((t.args[3]["C"] // 8) % cgb for t in tails):
+            while any((t.d["C"] // 8) % cgb for t in tails):
                 cgb //= 2
-            jobs = [dict(t.args[3], fused=0) for t in tails]
+            jobs = [dict(t.d, fused=0) for t in tails]
             if sync:  # the apply writes d(gamma), d(beta) / world (enable_sync_bn)
                 for j in jobs:
                     j["gscale"] = 1.0 / self.sync_bn_world
-            blocks = [t.args[2] * (t.args[3]["C"] // (8 * cgb)) for t in tails]
+            blocks = [t.nchunk * (t.d["C"] // (8 * cgb)) for t in tails]
             raw, nblocks, _ = lib().tail_table(jobs, blocks, True)
-            table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
-            self._tail_tables = getattr(self, "_tail_tables", [])
-            self._tail_tables.append(table)
+            table = self._device_table(raw)
             tag = f"tailbatch_{blk[len('fork:'):]}"
             red = Launch("tailbatchbwd_reduce", k_tail_bwd_batched, ACT_RELU, cgb, 1, table, len(jobs), nblocks,
                          owner=tails, stream=0)
@@ -509,22 +513,21 @@ class InceptionProgram(LoweredProgram):
         """enable_sync_bn drops the per-BN backward collective of every coalesced block's branch-output
         BNs and leaves ONE per block to batch_tails (autotune_program with batch_wgrads) -- raise if a step would
         run without it (those BNs would silently train on per-rank statistics).  StepRunner calls this."""
-        pending = getattr(self, "_sync_bwd_pending", None)
-        if pending:
-            raise RuntimeError(f"SyncBN: the coalesced backward collective of {len(pending)} Inception blocks was never "
-                               "inserted -- run batch_tails (autotune_program(..., batch_wgrads=True)) before stepping")
+        if self._sync_bwd_pending:
+            raise RuntimeError(f"SyncBN: the coalesced backward collective of {len(self._sync_bwd_pending)} Inception "
+                               "blocks was never inserted -- run batch_tails (autotune_program(..., batch_wgrads=True)) "
+                               "before stepping")
 
     def _tail_bwd_groups(self):
         """The block-output BN-tail backward launches batch_tails batches, per block (keyed by the block's
         backward fork pseudo-launch), and the index of each fork."""
         fork_at, groups, blk = {}, {}, None
         for i, l in enumerate(self.bwd.launches):
-            if l.name.startswith("fork:backward_f"):
+            if l.fork_tag.startswith("backward_f"):
                 blk = l.name
                 fork_at[blk] = i
-            elif (l.name.startswith("tailbwd") and isinstance(l.owner, CBR) and l.owner.defer_tail and blk is not None
-                  and l.args[3].get("fused", 0) in (0, 1) and l.args[0] == ACT_RELU and l.args[1] == 1
-                  and not l.args[3].get("side")):
+            elif (l.is_tail_bwd and isinstance(l.owner, CBR) and l.owner.defer_tail and blk is not None
+                  and l.d.get("fused", 0) in (0, 1) and l.kind == ACT_RELU and l.G == 1 and not l.d.get("side")):
                 groups.setdefault(blk, []).append(l)
         return fork_at, groups
 
@@ -535,7 +538,6 @@ class InceptionProgram(LoweredProgram):
         between the batched reduce and apply passes (batch_tails).  Blocks whose tails do not all batch
         (e.g. statistics fused into a data gradient) keep one collective per BN.  Returns the all-reduces per
         training step (Model C: 188 -> 126)."""
-        from .program import Launch
         skip_fwd = {P(bn.stats, bn.stats_off) for _, g in self._stat_groups for bn in g}
         _, groups = self._tail_bwd_groups()
         self._sync_part_groups = {}
@@ -551,7 +553,7 @@ class InceptionProgram(LoweredProgram):
         self._sync_allreduce = allreduce
         new = []
         for l in self.fwd_train.launches:
-            if l.name.startswith("tailbatch") and isinstance(l.owner, list):
+            if l.fn is k_tail_fwd_batched and isinstance(l.owner, list):
                 ptrs = {d["bn"]["stats"] for d, _ in l.owner}
                 for buf, bns in self._stat_groups:
                     if {P(bn.stats, bn.stats_off) for bn in bns} <= ptrs:
@@ -569,7 +571,7 @@ class InceptionProgram(LoweredProgram):
         the reason for NOL_MAX_PX -- and the cap does not apply (the stem's 47x122 / 21x58 consumers)."""
         from ..ops.functional import CONV_PATCH_CFG0, CONV_PATCH_NCFG, CONV_PATCHP_CFG0, CONV_PATCHP_NCFG, CONV_XCD
         from .tune import conv_signature, load_cache
-        if not hasattr(self, "_table"):
+        if self._table is None:
             self._table = load_cache()
         d = {"B": conv.B, "Hs": conv.Hi, "Ws": conv.Wi, "Ho": conv.Ho, "Wo": conv.Wo, "N": conv.Co, "Cs": conv.Cs,
              "KH": conv.KH, "KW": conv.KW, "sh": conv.sh, "sw": conv.sw, "ph": conv.ph, "pw": conv.pw,
@@ -631,7 +633,6 @@ class InceptionProgram(LoweredProgram):
         Returns the side-stream events the caller's next stream-0 launch must wait for.  With
         MDA_STREAMS=0 the annotations are inert and the ops run in list order."""
         owed0: List[str] = []       # last block's side-stream end events (joined at the next fork)
-        self._block_fork = getattr(self, "_block_fork", {})
         cur_block, used = None, set()
 
         def close_block():

@@ -19,8 +19,9 @@ from .program import (COMM_STREAM, SPILL_STREAM, Launch, Phase, k_adam, k_step_i
 ACT_NONE, ACT_RELU, ACT_SIGMOID, SIGMUL, ADD_RELU, POOL_RELU = range(6)
 
 
-def _wgrad_cost(cfg: int, G: int, d: dict) -> int:
-    """MFMA work (MACs incl. tile padding) of one weight-gradient launch -- used to balance fan-out."""
+def _wgrad_cost(l: Launch) -> int:
+    """MFMA work (MACs incl. tile padding) of one per-conv weight-gradient launch -- used to balance fan-out."""
+    cfg, G, d = l.args
     if cfg in WGRAD_PATCH:
         TN, CB, _, R = WGRAD_PATCH[cfg]
         px = d["splits"] * d["m_per_split"] * R * pad_to(d["Wo"], 8)
@@ -35,7 +36,7 @@ _GRAD_KEYS = ("dgamma", "dbeta", "dgamma2", "dbeta2", "dW", "db")
 def _grad_offsets(l, gbase: int, numel: int) -> List[int]:
     """Flat-gradient element offsets a launch writes directly (BN affine parameters of every group, the
     fc layer), found in its argument tree; conv weights are written by the finalize and not listed."""
-    G = l.args[1] if l.name.startswith("tailbwd") else (l.args[2] if l.name.startswith("conv_") else 1)
+    G = l.G
     out = []
 
     def walk(d):
@@ -53,6 +54,12 @@ def _grad_offsets(l, gbase: int, numel: int) -> List[int]:
 
     walk(l.args)
     return out
+
+
+def _insert_batches(keep: List[Launch], inserts: List[tuple]):
+    """Insert each (position, launches) of ``inserts`` into ``keep``; positions refer to ``keep`` as it is."""
+    for pos, batched in sorted(inserts, key=lambda x: -x[0]):
+        keep[pos:pos] = batched
 
 
 # pixels per thread of a forward BN-tail launch (its grid size; the kernel handles two per iteration)
@@ -79,6 +86,29 @@ class LoweredProgram:
     # when the overlapped share of the all-reduce (A: 40 %) exceeds that
     OVERLAP_MIN_MS = 0.05
 
+    def __init__(self):
+        """What a program keeps besides its model, buffers and phases -- the state the passes below share.
+        Subclasses call this first and declare their own in the same way."""
+        # device descriptor tables the launches point at (BN-tail, weight-gradient and finalize job tables,
+        # optimizer segments): alive as long as the program, so longer than any graph captured from it
+        self.keep_alive: list = []
+        self.wgfin_table = self.optseg_table = None  # the whole-program finalize / optimizer tables
+        self.opt_segs: List[dict] = []
+        self.src = None                # set_source
+        self.extra_state: list = []    # device state besides the flat buffers that a step mutates (snapshots)
+        self.stem_pack = (0, 0)        # (taps, offset) of the gather's vertical tap packing (core.stem_pack_geom)
+        self.sync_bn_world = None      # enable_sync_bn
+        self._n_routed = 0             # SyncBN collectives routed through stream 0 (_collective)
+        self._last_wgrad = None        # index of the backward's last per-conv weight gradient while it is emitted
+        self.buckets = None            # [(lo, hi)] of the flat gradient in completion order (segment_backward)
+        self.bucket_anchors = None     # stream_buckets: the launch each bucket is complete after
+        self.n_folded = self.n_dgrad_bnstats = self.n_wgrad_merged = self.n_wgrad_spilled = 0  # pass counters
+        self.data_parallel = False     # set_optimizer
+        self._opt_base = self._opt_hparams = self._opt_kwargs = None  # _emit_optimizer
+        self._early_adam: List[dict] = []  # argument dicts of the side streams' Adam launches (batch_wgrads)
+        self._step_early = None        # the step-counter launch's args once use_early_step_counter moved it
+        self._step_cursor = None       # set_step_cursor
+
     def dp_buckets(self, world: int, allreduce_ms: Optional[float] = None) -> int:
         """Gradient buckets of a data-parallel step of ``world`` ranks.  Every form of the step overlaps the
         buckets' all-reduces with the rest of the backward inside ONE step graph: captured collectives on the
@@ -87,7 +117,6 @@ class LoweredProgram:
         time of one all-reduce of the whole flat gradient measured on the live group at start-up
         (parallel.dist.calibrate_allreduce); below OVERLAP_MIN_MS one bucket.  Otherwise the model's
         default_buckets (A 2, C 4: SURVEY 5.8 sizes C's 83 MB in 2-4 buckets); MDA_BUCKETS overrides."""
-        import os
         if world <= 1:
             return self.LOCAL_BUCKETS
         if "MDA_BUCKETS" in os.environ:
@@ -106,21 +135,23 @@ class LoweredProgram:
         """One launch for several single-group forward tails of one kind (``jobs``: (args, blocks) from
         _tail_args; csrc/bn.hip tail_fwd_batched_kernel)."""
         raw, nblocks, max_c = lib().tail_table([d for d, _ in jobs], [b for _, b in jobs])
+        ph.add(f"tailbatch{kind}", k_tail_fwd_batched, kind, self._device_table(raw), len(jobs), nblocks, max_c,
+               owner=jobs)
+
+    def _device_table(self, raw: bytes) -> torch.Tensor:
+        """A host-built descriptor table on the device, kept alive with the program."""
         table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
-        self._tail_tables = getattr(self, "_tail_tables", [])
-        self._tail_tables.append(table)  # alive as long as the program (captured graphs point at it)
-        ph.add(f"tailbatch{kind}", k_tail_fwd_batched, kind, table, len(jobs), nblocks, max_c, owner=jobs)
+        self.keep_alive.append(table)
+        return table
 
     def _tail(self, ph: Phase, kind: int, G: int, y: Act, bn: BNLayer, out: Act, training: bool, r: Act = None,
               bn2: BNLayer = None, H=None, W=None):
-        d = {"y": y.p, "ygs": y.gs, "ldy": y.ld, "bn": bn.args(training), "out": out.p, "ogs": out.gs, "ldo": out.ld,
-             "B": self.B, "H": y.H if H is None else H, "W": y.W if W is None else W, "C": y.C}
+        d, blocks = self._tail_args(y, bn, out, training, H, W)
         if r is not None:
             d.update({"r": r.p, "rgs": r.gs, "ldr": r.ld})
         if bn2 is not None:
             d["bn2"] = bn2.args(training)
-        M = self.B * d["H"] * d["W"]
-        ph.add(f"tail{kind}", k_tail_fwd, kind, G, _blocks(M, y.C, per_thread=TAIL_PX_PER_THREAD), d)
+        ph.add(f"tail{kind}", k_tail_fwd, kind, G, blocks, d)
 
     def _tail_bwd(self, ph: Phase, kind: int, G: int, y: Act, bn: BNLayer, g: list, dy: Act, r: Act = None,
                   bn2: BNLayer = None, side: Act = None, dy2: Act = None):
@@ -179,7 +210,7 @@ class LoweredProgram:
         new = []
         for l in self.fwd_train.launches:
             new.append(l)
-            st = l.args[3].get("stats") or 0 if l.name == "conv_fwd" else 0
+            st = l.d.get("stats") or 0 if l.is_conv_fwd else 0
             bn = by_stats.get(st) if st not in skip_fwd else None
             if bn is not None:
                 new += self._collective(allreduce, bn.used_stats(), l.stream, l.bucket, l.record)
@@ -187,8 +218,11 @@ class LoweredProgram:
                 n += 1
         self.fwd_train.launches = new
         new = []
+        dz_keys = ("dzbuf", "dzgs", "lddz")  # the stored dz: the apply after a collective re-evaluates it
+        out_keys = ("dy", "dgs", "ldd", "side", "sgs", "lds", "dgamma", "dbeta", "dgamma2", "dbeta2", "dy2", "d2gs",
+                    "ldd2", "pgs")           # what only the apply pass writes
         for l in self.bwd.launches:
-            if not l.name.startswith("tailbwd") or l.args[3].get("fused") == 3 or l.args[3]["part"] in skip_bwd:
+            if not l.is_tail_bwd or l.d.get("fused") == 3 or l.d["part"] in skip_bwd:
                 new.append(l)
                 continue
             kind, G, nchunk, d = l.args
@@ -198,19 +232,17 @@ class LoweredProgram:
             # identity: bucket-cut anchors refer to it), the apply carries its event
             l.record = None
             if d.get("fused", 0) != 2:  # statistics of this tail: a reduce-only pass first
-                red = {k: v for k, v in d.items() if k not in ("dzbuf", "dzgs", "lddz", "dy", "dgs", "ldd", "side",
-                                                                "sgs", "lds", "dgamma", "dbeta", "dgamma2", "dbeta2",
-                                                                "dy2", "d2gs", "ldd2", "pgs")}
+                red = {k: v for k, v in d.items() if k not in dz_keys + out_keys}
                 red["fused"] = 3
-                l.name, l.args = f"tailpart{kind}", (kind, G, nchunk, red)
+                l.rewrite(f"tailpart{kind}", l.fn, kind, G, nchunk, red)
                 new += [l] + self._collective(allreduce, bn.used_part(), l.stream, l.bucket)
             elif l.stream < self.COLLECTIVE_STREAMS:  # statistics from the producing dgrad's epilogue
-                l.name, l.fn, l.args = "allreduce_bn", k_allreduce, (allreduce, bn.used_part())
+                l.rewrite("allreduce_bn", k_allreduce, allreduce, bn.used_part())
                 new.append(l)
             else:  # (the launch keeps its waits as a kernel-free fork point in front of the collective)
-                l.name, l.fn, l.args = f"fork:{l.name}", None, ()
+                l.rewrite(f"fork:{l.name}", None)
                 new += [l] + self._collective(allreduce, bn.used_part(), l.stream, l.bucket)
-            d = {k: v for k, v in d.items() if k not in ("dzbuf", "dzgs", "lddz")}
+            d = {k: v for k, v in d.items() if k not in dz_keys}
             d["fused"], d["gscale"] = 2, 1.0 / world
             new.append(Launch(name, k_tail_bwd, kind, G, nchunk, d, owner=l.owner, stream=l.stream, record=record,
                               bucket=l.bucket))
@@ -230,7 +262,7 @@ class LoweredProgram:
         ``record``: the event the last of them records (the tag the replaced launch carried)."""
         if stream < self.COLLECTIVE_STREAMS:
             return [Launch("allreduce_bn", k_allreduce, allreduce, t, stream=stream, record=record, bucket=bucket)]
-        self._n_routed = getattr(self, "_n_routed", 0) + 1
+        self._n_routed += 1
         tp, ta = f"sbn_p{self._n_routed}", f"sbn_a{self._n_routed}"
         return [Launch(f"fork:{tp}", None, stream=stream, record=tp, bucket=bucket),
                 Launch("allreduce_bn", k_allreduce, allreduce, t, stream=0, waits=(tp,), record=ta, bucket=bucket),
@@ -242,7 +274,6 @@ class LoweredProgram:
         single-consumer output of a BN + ReLU tail reads the pre-BN y and applies the BN affine + ReLU to its
         im2col operand (and so does its weight gradient), so that tail is never launched (csrc/conv.hip
         MODE_FWD_NOL)."""
-        import os
         return os.environ.get("MDA_NOL", "1") == "1"
 
     # Normalise-on-load only for consumer convs with at most this many output pixels (B*Ho*Wo): on the
@@ -284,28 +315,24 @@ class LoweredProgram:
         The tail then qualifies for fuse_dgrad_bn_stats -- the statistics come from the dgrad epilogue and
         the tail runs apply-only: Model A's residual-block ADD_RELU tails lose their reduce pass and their
         re-reads of four fp32 sources.  Returns the number of folded tails."""
-        import os
         self.n_folded = 0
         if not self.FOLD_SOURCES or os.environ.get("MDA_FOLD", "1") != "1":
             return 0
         ls = self.bwd.launches
-        recorded_at = {}  # event tag -> index of the launch that records it
-        for i, l in enumerate(ls):
-            if l.record is not None:
-                recorded_at[l.record] = i
+        recorded_at = {l.record: i for i, l in enumerate(ls) if l.record is not None}  # tag -> recording launch
         last_dgrad = {}  # stream -> (index, launch) of its latest dgrad
         for i, l in enumerate(ls):
-            if l.name == "conv_dgrad":
+            if l.is_dgrad:
                 last_dgrad[l.stream] = (i, l)
                 continue
-            if not l.name.startswith("tailbwd"):
+            if not l.is_tail_bwd:
                 continue
             kind, G, nchunk, d = l.args
             g = d["g"]
             if kind not in (ACT_NONE, ACT_RELU, ADD_RELU) or not 2 <= len(g) <= 4 or l.stream not in last_dgrad:
                 continue
             j, D = last_dgrad[l.stream]
-            if any(k.stream == l.stream and k.name not in ("conv_wgrad",) for k in ls[j + 1:i]):
+            if any(k.stream == l.stream and not k.is_wgrad for k in ls[j + 1:i]):
                 continue  # something else runs between the dgrad and the tail
             mode, cfg, PG, pd = D.args
             mine = [q for q, (p, gs, ld) in enumerate(g) if p == pd["out"] and gs == pd["ogs"] and ld == pd["ldo"]]
@@ -339,9 +366,9 @@ class LoweredProgram:
         self.n_dgrad_bnstats = 0
         producers = {}
         for l in self.bwd.launches:
-            if l.name == "conv_dgrad":
-                producers[l.args[3]["out"]] = l
-            elif l.name.startswith("tailbwd"):
+            if l.is_dgrad:
+                producers[l.d["out"]] = l
+            elif l.is_tail_bwd:
                 kind, G, nchunk, d = l.args
                 if kind not in (ACT_NONE, ACT_RELU, ACT_SIGMOID, ADD_RELU) or len(d["g"]) != 1 or d.get("dzbuf"):
                     continue
@@ -366,8 +393,6 @@ class LoweredProgram:
     def set_source(self, X: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor):
         """Bind the dataset tensors the gather launch reads (X [N,C,H,W] fp32, labels [N,2], idx [B])."""
         self.src = (X, labels, idx)
-
-    stem_pack = (0, 0)  # (taps, offset) of the gather's vertical tap packing (core.stem_pack_geom)
 
     def gather_phase(self, X, labels, idx, clear: bool = False, cursor=None) -> Phase:
         """The batch gather; ``clear``: the same launch also zeroes the arena's zeroed region (what
@@ -453,16 +478,15 @@ class LoweredProgram:
                                            self.device)
         if convs is None:
             self.wgfin_table = t
-        self._fin_tables = getattr(self, "_fin_tables", {})
-        self._fin_tables[id(convs)] = t  # keep the device table alive for the captured graphs
+        self.keep_alive.append(t)
         return t, nd, nblocks
 
     def refresh_wgrad_finalize(self):
         """Rebuild the finalize descriptor table(s) after wgrad configs (split counts) changed.  A finalize
         launch's ``owner`` lists the convs it reduces (a gradient bucket's); None means every conv."""
         for l in self.bwd.launches:
-            if l.name == "wgrad_finalize":
-                l.args = self._wgfin_args(l.owner)
+            if l.is_finalize:
+                l.rewrite(l.name, l.fn, *self._wgfin_args(l.owner))
 
     # ---- gradient buckets (data parallelism, SURVEY 5.8 / C2) ---------------------------------------
     def bucket_cut_candidates(self) -> List[tuple]:
@@ -485,7 +509,7 @@ class LoweredProgram:
         f = self.flat
         self.buckets = [(0, f.numel)]
         self.bucket_anchors = None
-        if n_buckets <= 1 or any(l.name == "cut" for l in self.bwd.launches):
+        if n_buckets <= 1 or any(l.is_cut for l in self.bwd.launches):
             return self.buckets
         ls = self.bwd.launches
         cands = [c for c in self.bucket_cut_candidates() if 0 < c[2] - c[1] < f.numel]
@@ -521,14 +545,14 @@ class LoweredProgram:
         if anchors != sorted(anchors):
             raise ValueError("bucket cut anchors out of backward order")
         seg_of = lambda i: sum(1 for a in anchors if a <= i)  # noqa: E731
-        fin = next(i for i, l in enumerate(ls) if l.name == "wgrad_finalize")
+        fin = next(i for i, l in enumerate(ls) if l.is_finalize)
         if fin != len(ls) - 1:
             raise ValueError("the weight-gradient finalize must be the backward's last launch")
         # every gradient writer must run no later than its bucket's piece
         gbase = P(f.grads)
         for i, l in enumerate(ls[:fin]):
             seg = seg_of(i)
-            if l.name == "conv_wgrad":
+            if l.is_wgrad:
                 bs = {bucket_of(f.off(m.weight)) for m in l.owner.mods}
                 if len(bs) != 1 or seg > min(bs):
                     raise ValueError(f"weight gradient of a bucket-{bs} conv runs in backward piece {seg}")
@@ -571,7 +595,7 @@ class LoweredProgram:
         on a backward that segment_backward left whole.  Returns the buckets [(lo, hi)] in completion order."""
         f = self.flat
         ls = self.bwd.launches
-        if any(l.name == "cut" for l in ls):
+        if any(l.is_cut for l in ls):
             raise ValueError("stream_buckets needs an uncut backward (segment_backward(1))")
         writers, side_fin = self._grad_writers()
         buckets, anchors, k, lo = [], [], 0, 0
@@ -595,11 +619,11 @@ class LoweredProgram:
             buckets.append((lo, hi))
             anchors.append(ls[side_fin[st]])
             lo, k = hi, j
-        fins = [l for l in ls if l.name == "wgrad_finalize"]
+        fins = [l for l in ls if l.is_finalize]
         buckets.append((lo, f.numel))
         # the remainder is complete once every stream has joined stream 0 after its finalize (batch_wgrads)
         after = ls[ls.index(fins[-1]) + 1] if ls.index(fins[-1]) + 1 < len(ls) else None
-        anchors.append(after if after is not None and after.name == "join_side" else fins[-1])
+        anchors.append(after if after is not None and after.is_join else fins[-1])
         self.buckets, self.bucket_anchors = buckets, anchors
         return buckets
 
@@ -611,7 +635,7 @@ class LoweredProgram:
         gbase = P(f.grads)
         writers: Dict[int, set] = {}
         for i, l in enumerate(self.bwd.launches):
-            if l.name == "wgrad_finalize":
+            if l.is_finalize:
                 for c in (l.owner or self.convs):  # (no owner: the finalize covers every conv)
                     for m in c.mods:
                         writers.setdefault(f.off(m.weight), set()).add((l.stream, i))
@@ -621,8 +645,7 @@ class LoweredProgram:
                 for src in srcs:
                     for off in _grad_offsets(src, gbase, f.numel):
                         writers.setdefault(off, set()).add((l.stream, i))
-        side_fin = {l.stream: i for i, l in enumerate(self.bwd.launches)
-                    if l.name == "wgrad_finalize" and l.stream != 0}
+        side_fin = {l.stream: i for i, l in enumerate(self.bwd.launches) if l.is_finalize and l.stream != 0}
         return writers, side_fin
 
     def stream_param_order(self) -> Optional[list]:
@@ -655,26 +678,35 @@ class LoweredProgram:
         through the phase-end join of the communication stream.  ``allreduce`` must be stream-ordered
         (DistContext.all_reduce_ordered_; captured on RCCL)."""
         f = self.flat
-        buckets = getattr(self, "buckets", None) or [(0, f.numel)]
-        ph = Phase("backward_dp")
+        buckets = self.buckets or [(0, f.numel)]
+
+        def collective(fin, tags):
+            lo, hi = buckets[fin.bucket]
+            return Launch("allreduce_grads", k_allreduce, allreduce, f.grads[lo:hi], stream=COMM_STREAM,
+                          waits=tuple(tags), bucket=fin.bucket)
+        return self._backward_with_bucket_hook("backward_dp", buckets, collective)
+
+    def _backward_with_bucket_hook(self, name: str, buckets: List[tuple], hook) -> Phase:
+        """A copy of the backward without its cut markers in which every finalize records an event and the launch
+        ``hook(fin, tags)`` follows each bucket's LAST finalize ``fin`` (a bucket may be finalized by several
+        streams, SIDE_FINALIZE); ``tags``: the events of the bucket's finalizes, ``fin``'s own last.  The
+        program's own backward is left untouched."""
+        ph = Phase(name)
         ph.alias = dict(self.bwd.alias)
-        fins = [l for l in self.bwd.launches if l.name == "wgrad_finalize"]
-        last = {l.bucket: l for l in fins}  # a bucket may be finalized by several streams (SIDE_FINALIZE)
+        last = {l.bucket: l for l in self.bwd.launches if l.is_finalize}
         done = {}
         for l in self.bwd.launches:
-            if l.name == "cut":
+            if l.is_cut:
                 continue
-            if l.name != "wgrad_finalize":
+            if not l.is_finalize:
                 ph.launches.append(l)
                 continue
-            tag = l.record or f"bucket{l.bucket}_grads_{len(done.get(l.bucket, []))}"
+            tags = done.setdefault(l.bucket, [])
+            tags.append(l.record or f"bucket{l.bucket}_grads_{len(tags)}")
             ph.launches.append(Launch(l.name, l.fn, *l.args, owner=l.owner, stream=l.stream, waits=l.waits,
-                                      record=tag, bucket=l.bucket))
-            done.setdefault(l.bucket, []).append(tag)
+                                      record=tags[-1], bucket=l.bucket))
             if l is last[l.bucket]:
-                lo, hi = buckets[l.bucket]
-                ph.launches.append(Launch("allreduce_grads", k_allreduce, allreduce, f.grads[lo:hi],
-                                          stream=COMM_STREAM, waits=tuple(done[l.bucket]), bucket=l.bucket))
+                ph.launches.append(hook(l, tags))
         if sorted(done) != list(range(len(buckets))):
             raise ValueError(f"finalize launches for buckets {sorted(done)}, expected {len(buckets)} buckets")
         return ph
@@ -688,39 +720,22 @@ class LoweredProgram:
         backward -- overlap without capturing multi-rank collectives.  Buckets from stream_buckets: the event
         follows the bucket's side-stream finalize; from segment_backward: it follows the bucket's last finalize,
         joined over the finalizes' streams."""
-        f = self.flat
-        buckets = getattr(self, "buckets", None) or [(0, f.numel)]
+        buckets = self.buckets or [(0, self.flat.numel)]
         if len(events) != len(buckets):
             raise ValueError(f"{len(events)} events for {len(buckets)} buckets")
-        ph = Phase("backward_ext")
-        ph.alias = dict(self.bwd.alias)
-        anchors = getattr(self, "bucket_anchors", None)
+        anchors = self.bucket_anchors
         if anchors is not None and len(anchors) == len(buckets):
+            ph = Phase("backward_ext")
+            ph.alias = dict(self.bwd.alias)
             at = {id(a): k for k, a in enumerate(anchors)}
             for l in self.bwd.launches:
                 ph.launches.append(l)
                 if id(l) in at:
                     ph.launches.append(Launch("ext_record", k_ext_record, events[at[id(l)]], stream=l.stream))
             return ph
-        fins = [l for l in self.bwd.launches if l.name == "wgrad_finalize"]
-        last = {l.bucket: l for l in fins}
-        done = {}
-        for l in self.bwd.launches:
-            if l.name == "cut":
-                continue
-            if l.name != "wgrad_finalize":
-                ph.launches.append(l)
-                continue
-            tag = l.record or f"bucket{l.bucket}_grads_{len(done.get(l.bucket, []))}"
-            ph.launches.append(Launch(l.name, l.fn, *l.args, owner=l.owner, stream=l.stream, waits=l.waits,
-                                      record=tag, bucket=l.bucket))
-            done.setdefault(l.bucket, []).append(tag)
-            if l is last[l.bucket]:
-                ph.launches.append(Launch("ext_record", k_ext_record, events[l.bucket], stream=l.stream,
-                                          waits=tuple(t for t in done[l.bucket] if t != tag), bucket=l.bucket))
-        if sorted(done) != list(range(len(buckets))):
-            raise ValueError(f"finalize launches for buckets {sorted(done)}, expected {len(buckets)} buckets")
-        return ph
+        return self._backward_with_bucket_hook("backward_ext", buckets, lambda fin, tags: Launch(
+            "ext_record", k_ext_record, events[fin.bucket], stream=fin.stream,
+            waits=tuple(t for t in tags if t != tags[-1]), bucket=fin.bucket))
 
     WGRAD_MAX_BATCHES = 3
     # the same cap for stream 0 only (its batches run serially after the data-gradient chain); None: as above
@@ -738,7 +753,7 @@ class LoweredProgram:
         The cap is WGRAD_MAX_BATCHES (swept 1/2/3/4/none in docs/PERF.md).  Returns the number of convs moved."""
         if max_batches is None:
             max_batches = self.WGRAD_MAX_BATCHES
-        wg = [l for l in self.bwd.launches if l.name == "conv_wgrad" and l.owner is not None]
+        wg = [l for l in self.bwd.launches if l.is_wgrad and l.owner is not None]
         moved = 0
         # one batch set per (gradient bucket, stream): a segmented backward batches each bucket separately
         for bk, st in sorted({(l.bucket, l.stream) for l in wg}):
@@ -747,10 +762,10 @@ class LoweredProgram:
             while True:
                 groups = {}
                 for l in mine:
-                    groups.setdefault(l.args[0], []).append(l)
+                    groups.setdefault(l.cfg, []).append(l)
                 if len(groups) <= cap:
                     break
-                cost = {c: sum(_wgrad_cost(c, l.args[1], l.args[2]) for l in ls) for c, ls in groups.items()}
+                cost = {c: sum(_wgrad_cost(l) for l in ls) for c, ls in groups.items()}
                 move = None
                 for c in sorted(groups, key=lambda c: cost[c]):
                     targets = [t for t in groups if t != c and all(l.owner.wgrad_valid(t) for l in groups[c])]
@@ -760,8 +775,7 @@ class LoweredProgram:
                 if move is None:
                     break
                 for l in groups[move[0]]:
-                    l.owner.set_wgrad_cfg(move[1])
-                    l.args = (move[1],) + tuple(l.args[1:])
+                    l.set_cfg(move[1])
                     moved += 1
         self.n_wgrad_merged = moved
         return moved
@@ -785,13 +799,13 @@ class LoweredProgram:
         (table entry wgspill|..., percent; 0 = off).  Must run before merge_wgrad_cfgs / batch_wgrads; a
         backward cut into gradient-bucket pieces is left alone.  Returns the number of convs moved."""
         ls = self.bwd.launches
-        if frac <= 0 or any(l.name == "cut" for l in ls):
+        if frac <= 0 or any(l.is_cut for l in ls):
             return 0
-        wg0 = [l for l in ls if l.name == "conv_wgrad" and l.stream == 0]
+        wg0 = [l for l in ls if l.is_wgrad and l.stream == 0]
         # a launch recording an event (other than the per-conv "wgrads" tag) ends the movable prefix
         cut = next((i for i, l in enumerate(wg0) if l.record not in (None, "wgrads")), len(wg0))
         wg0 = wg0[:cut]
-        cost = [_wgrad_cost(l.args[0], l.args[1], l.args[2]) for l in wg0]
+        cost = [_wgrad_cost(l) for l in wg0]
         total, acc, n = sum(cost), 0, 0
         while n < len(wg0) and acc + cost[n] <= frac * total:
             acc += cost[n]
@@ -810,8 +824,6 @@ class LoweredProgram:
     # C +0.6-7.5 % / A neutral, and A +0.3-0.6 % / C neutral (docs/PERF.md round 4); class switches for A/B runs
     SIDE_FINALIZE = True
     EARLY_ADAM = True
-    # stream 0's tail finalize waits for every side stream's last launch (the round-5 form; class switch)
-    JOIN_AT_FINALIZE = False
 
     def batch_wgrads(self):
         """Replace the per-conv weight-gradient launches by batched launches, one per (stream, tile
@@ -820,43 +832,16 @@ class LoweredProgram:
         Model A's level-branch weight gradients overlap the backbone's backward.  Called after the
         autotuner has fixed every conv's wgrad config and split count."""
         ls = self.bwd.launches
-        wg = [l for l in ls if l.name == "conv_wgrad"]
+        wg = [l for l in ls if l.is_wgrad]
         if not wg:
             return
-        if any(l.name == "cut" for l in ls):
+        if any(l.is_cut for l in ls):
             return self._batch_wgrads_segmented()
-        fin = next(i for i, l in enumerate(ls) if l.name == "wgrad_finalize")
-        keep = []
-        for l in ls[:fin]:
-            if l.name != "conv_wgrad":
-                keep.append(l)
-                continue
-            if l.record is not None and l.record != "wgrads":
-                # an event recorded on a removed launch now stands for the stream's previous kept launch
-                prev = next((k for k in reversed(keep) if k.stream == l.stream), None)
-                if prev is None:
-                    raise RuntimeError(f"cannot re-anchor event {l.record}")
-                if prev.record is None:
-                    prev.record = l.record
-                else:
-                    self.bwd.alias[l.record] = prev.record
-        self.wgrad_tables = []
-        inserts, tags = [], []
-        for st in sorted({l.stream for l in wg}):
-            batched = []
-            for cfg in sorted({l.args[0] for l in wg if l.stream == st}):
-                group = [l for l in wg if l.stream == st and l.args[0] == cfg]
-                batched.append(self._wgrad_batch_launch(cfg, group, st))
-            # the jobs' own waits (spilled weight gradients: the spill point) go on the stream's first batch
-            batched[0].waits = tuple(dict.fromkeys(w for l in wg if l.stream == st for w in l.waits))
-            # list position = capture order, which the graph executor follows when it dispatches: a batch
-            # goes right after its stream's last kernel or the launch recording what it waits for (a spilled
-            # batch appended at the end of the list started after stream 0's whole chain)
-            pos = max([i for i, k in enumerate(keep) if k.stream == st or (k.record and k.record in batched[0].waits)],
-                      default=len(keep) - 1) + 1
-            batched[-1].record = f"wgrads_s{st}"
-            tags.append(batched[-1].record)
-            inserts.append((pos, batched))
+        fin = next(i for i, l in enumerate(ls) if l.is_finalize)
+        keep = self._drop_wgrads(ls[:fin], retired=("wgrads",))  # (only a weight gradient records "wgrads")
+        inserts = [self._batch_stream_wgrads([l for l in wg if l.stream == st], st, keep, f"wgrads_s{st}")
+                   for st in sorted({l.stream for l in wg})]
+        tags = [batched[-1].record for _, batched in inserts]
         if self.SIDE_FINALIZE:
             # every side stream reduces its own convs' split slabs right after its batches (overlapping
             # stream 0's remaining chain); the tail finalize keeps stream 0's convs
@@ -864,54 +849,38 @@ class LoweredProgram:
             for l in wg:
                 if l.stream != 0 and l.owner is not None:
                     side.setdefault(l.stream, []).append(l.owner)
-            for pos_batched in inserts:
-                batched = pos_batched[1]
-                st = batched[-1].stream
-                if st in side:
-                    convs = list(dict.fromkeys(side[st]))
-                    tag = f"wgfin_s{st}"
-                    batched.append(Launch("wgrad_finalize", k_wgfin, *self._wgfin_args(convs), owner=convs, stream=st,
-                                          record=tag))
-                    tags = [t for t in tags if t != batched[-2].record] + [tag]
+            # single process: the side convs' Adam + re-pack right after their finalize, on their stream
+            # (the optimizer phase then covers the rest); with gradient averaging (DP, set_optimizer's
+            # data_parallel) the update must wait for the all-reduce, so it stays in the optimizer phase
             early_ok = self.EARLY_ADAM and not self.data_parallel and self._opt_hparams.get("grad_scale", 1.0) == 1.0
-            done = [c for v in side.values() for c in v]
-            rest = [c for c in self.convs if c not in done]
+            early = set()
+            for _, batched in inserts:
+                st = batched[-1].stream
+                if st not in side:
+                    continue
+                tags.remove(batched[-1].record)  # the join waits for the stream's last launch only
+                convs = list(dict.fromkeys(side[st]))
+                batched.append(Launch("wgrad_finalize", k_wgfin, *self._wgfin_args(convs), owner=convs, stream=st,
+                                      record=f"wgfin_s{st}"))
+                if early_ok:
+                    offs = {self.flat.off(m.weight) for c in convs for m in c.mods}
+                    early |= offs
+                    d = dict(self._opt_segs_args([g for g in self.opt_segs if g["kind"] == 3 and g["off"] in offs]),
+                             update=1, inc_step=0, t_pre=int(self._step_early is not None), **self._opt_hparams)
+                    batched.append(Launch("adam_pack_early", k_adam, d, stream=st, record=f"adam_s{st}"))
+                    self._early_adam.append(d)
+                tags.append(batched[-1].record)
+            rest = [c for c in self.convs if not any(c in v for v in side.values())]
             if side and rest:
                 ls[fin].owner = rest
-                ls[fin].args = self._wgfin_args(rest)
-            if side and early_ok:
-                # single process: the side convs' Adam + re-pack right after their finalize, on their stream
-                # (the optimizer phase then covers the rest); with gradient averaging (DP, set_optimizer's
-                # data_parallel) the update must wait for the all-reduce, so it stays in the optimizer phase
-                early = set()
-                for pos_batched in inserts:
-                    batched = pos_batched[1]
-                    st = batched[-1].stream
-                    if st not in side:
-                        continue
-                    offs = {self.flat.off(m.weight) for c in side[st] for m in c.mods}
-                    segs = [g for g in self.opt_segs if g["kind"] == 3 and g["off"] in offs]
-                    early |= offs
-                    table, ns, nb = build_optseg_table(segs, self.device)
-                    self._opt_tables = getattr(self, "_opt_tables", []) + [table]
-                    d = dict(self._opt_base, segs=P(table), nsegs=ns, nblocks=nb, update=1, inc_step=0,
-                             t_pre=int(self._step_early is not None), **self._opt_hparams)
-                    tag = f"adam_s{st}"
-                    batched.append(Launch("adam_pack_early", k_adam, d, stream=st, record=tag))
-                    tags = [t for t in tags if t != f"wgfin_s{st}"] + [tag]
-                    self._early_adam = getattr(self, "_early_adam", []) + [d]
-                segs = [g for g in self.opt_segs if not (g["kind"] == 3 and g["off"] in early)]
-                table, ns, nb = build_optseg_table(segs, self.device)
-                self._opt_tables = getattr(self, "_opt_tables", []) + [table]
-                self._opt_base = dict(self._opt_base, segs=P(table), nsegs=ns, nblocks=nb)
+                ls[fin].rewrite(ls[fin].name, k_wgfin, *self._wgfin_args(rest))
+            if early:
+                self._opt_base = self._opt_segs_args([g for g in self.opt_segs
+                                                      if not (g["kind"] == 3 and g["off"] in early)])
                 self.set_optimizer(**self._opt_kwargs)
-        for pos, batched in sorted(inserts, key=lambda x: -x[0]):
-            keep[pos:pos] = batched
-        for l in keep:  # the per-conv "wgrads" event is gone
-            if l.record == "wgrads":
-                l.record = None
+        _insert_batches(keep, inserts)
         side_tags = tuple(t for t in tags if t != "wgrads_s0")
-        if self.SIDE_FINALIZE and side and not self.JOIN_AT_FINALIZE:
+        if self.SIDE_FINALIZE and side:
             # stream 0's finalize reduces stream 0's convs only: it follows its own batches in stream order, and
             # the side streams (their finalize, early Adam) join stream 0 after it -- a pseudo-launch, the last
             # bucket's anchor (stream_buckets) -- instead of delaying it (A: the tail finalize waited ~20 us
@@ -922,14 +891,51 @@ class LoweredProgram:
         else:
             ls[fin].waits = tuple(tags)
             self.bwd.launches = keep + ls[fin:]
-        self.wgrads_batched = True
+
+    def _opt_segs_args(self, segs: List[dict]) -> dict:
+        """The optimizer launch's base arguments pointed at a device table of ``segs`` only."""
+        table, ns, nb = build_optseg_table(segs, self.device)
+        self.keep_alive.append(table)
+        return dict(self._opt_base, segs=P(table), nsegs=ns, nblocks=nb)
+
+    def _drop_wgrads(self, ls: List[Launch], retired=()) -> List[Launch]:
+        """``ls`` without its per-conv weight gradients.  An event recorded on a removed launch now stands for
+        the stream's previous kept launch: that launch records it, or, where it records one already, the phase
+        aliases the tag to that one.  ``retired``: tags the caller gives up instead."""
+        keep = []
+        for l in ls:
+            if not l.is_wgrad:
+                keep.append(l)
+            elif l.record is not None and l.record not in retired:
+                prev = next((k for k in reversed(keep) if k.stream == l.stream), None)
+                if prev is None:
+                    raise RuntimeError(f"cannot re-anchor event {l.record}")
+                if prev.record is None:
+                    prev.record = l.record
+                else:
+                    self.bwd.alias[l.record] = prev.record
+        return keep
+
+    def _batch_stream_wgrads(self, wg: List[Launch], st: int, keep: List[Launch], tag: str, bucket: int = 0) -> tuple:
+        """Stream ``st``'s per-conv weight gradients ``wg`` as one batched launch per tile config, the last of
+        them recording ``tag``.  Returns (position in ``keep``, launches) for _insert_batches."""
+        batched = [self._wgrad_batch_launch(cfg, [l for l in wg if l.cfg == cfg], st, bucket)
+                   for cfg in sorted({l.cfg for l in wg})]
+        # the jobs' own waits (spilled weight gradients: the spill point) go on the stream's first batch
+        batched[0].waits = tuple(dict.fromkeys(w for l in wg for w in l.waits))
+        batched[-1].record = tag
+        # list position = capture order, which the graph executor follows when it dispatches: a batch
+        # goes right after its stream's last kernel or the launch recording what it waits for (a spilled
+        # batch appended at the end of the list started after stream 0's whole chain)
+        pos = max([i for i, k in enumerate(keep) if k.stream == st or (k.record and k.record in batched[0].waits)],
+                  default=len(keep) - 1) + 1
+        return pos, batched
 
     def _wgrad_batch_launch(self, cfg: int, group: List[Launch], st: int, bucket: int = 0) -> Launch:
-        raw, nblocks = lib().wgrad_table(cfg, [l.args[2] for l in group], [l.args[1] for l in group])
-        table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
-        self.wgrad_tables.append(table)
+        raw, nblocks = lib().wgrad_table(cfg, [l.d for l in group], [l.G for l in group])
         cap = self.SIDE_WGRAD_GRID if st != 0 else 0
-        return Launch("wgrad_batched", k_wgrad_batched, cfg, table, len(group), nblocks, cap, stream=st, bucket=bucket)
+        return Launch("wgrad_batched", k_wgrad_batched, cfg, self._device_table(raw), len(group), nblocks, cap,
+                      stream=st, bucket=bucket)
 
     def _batch_wgrads_segmented(self):
         """batch_wgrads for a backward cut into gradient-bucket pieces (segment_backward): in every piece,
@@ -937,58 +943,33 @@ class LoweredProgram:
         stream's last launch of the piece (a stream without launches there uses stream 0), and the piece's
         finalize waits for those batches.  Weight gradients of a later bucket whose launches sat in an
         earlier piece move to their bucket's piece (their dy is complete by then)."""
-        ls = self.bwd.launches
-        pieces, cur = [], []
-        for l in ls:
-            if l.name == "cut":
-                pieces.append(cur)
-                cur = []
+        pieces = [[]]
+        for l in self.bwd.launches:
+            if l.is_cut:
+                pieces.append([])
             else:
-                cur.append(l)
-        pieces.append(cur)
+                pieces[-1].append(l)
         by_bucket: Dict[int, List[Launch]] = {}
-        kept_pieces = []
-        for piece in pieces:
-            keep = []
-            for l in piece:
-                if l.name != "conv_wgrad":
-                    keep.append(l)
-                    continue
+        for l in self.bwd.launches:
+            if l.is_wgrad:
                 by_bucket.setdefault(l.bucket, []).append(l)
-                if l.record is not None:  # the event now stands for the stream's previous kept launch
-                    prev = next((k for k in reversed(keep) if k.stream == l.stream), None)
-                    if prev is None:
-                        raise RuntimeError(f"cannot re-anchor event {l.record}")
-                    if prev.record is None:
-                        prev.record = l.record
-                    else:
-                        self.bwd.alias[l.record] = prev.record
-            kept_pieces.append(keep)
-        self.wgrad_tables = []
         out = []
-        for k, keep in enumerate(kept_pieces):
+        for k, keep in enumerate([self._drop_wgrads(piece) for piece in pieces]):
             fin = keep.pop()  # segment_backward put the bucket's finalize last in its piece
-            assert fin.name == "wgrad_finalize" and fin.bucket == k, fin.name
+            assert fin.is_finalize and fin.bucket == k, fin.name
             mine = by_bucket.get(k, [])
             streams_here = {l.stream for l in keep}
             for l in mine:
                 if l.stream not in streams_here:
                     l.stream = 0
-            tags = []
-            for st in sorted({l.stream for l in mine}):
-                batched = [self._wgrad_batch_launch(cfg, [l for l in mine if l.stream == st and l.args[0] == cfg],
-                                                    st, k)
-                           for cfg in sorted({l.args[0] for l in mine if l.stream == st})]
-                batched[-1].record = f"wgrads_b{k}_s{st}"
-                tags.append(batched[-1].record)
-                pos = max((i for i, l in enumerate(keep) if l.stream == st), default=len(keep) - 1) + 1
-                keep[pos:pos] = batched
-            fin.waits = tuple(fin.waits) + tuple(tags)
+            inserts = [self._batch_stream_wgrads([l for l in mine if l.stream == st], st, keep, f"wgrads_b{k}_s{st}", k)
+                       for st in sorted({l.stream for l in mine})]
+            fin.waits = tuple(fin.waits) + tuple(batched[-1].record for _, batched in inserts)
+            _insert_batches(keep, inserts)
             out += keep + [fin]
-            if k < len(kept_pieces) - 1:
+            if k < len(pieces) - 1:
                 out.append(Launch("cut", None))
         self.bwd.launches = out
-        self.wgrads_batched = True
 
     def _emit_optimizer(self, grad_scale: float = 1.0) -> Dict[str, Phase]:
         f = self.flat
@@ -998,14 +979,11 @@ class LoweredProgram:
         base = {"p": P(f.params), "g": P(f.grads), "m": P(f.exp_avg), "v": P(f.exp_avg_sq), "n": f.numel,
                 "lr": P(f.lr), "step": P(f.step), "segs": P(self.optseg_table), "nsegs": ns, "nblocks": nblocks}
         self._opt_base = base
-        self._opt_hparams = dict(b1=0.9, b2=0.999, eps=1e-8, wd=0.0, grad_scale=grad_scale)
-        self._opt_kwargs = dict(betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=grad_scale)
-        self.data_parallel = False
-        upd = Phase("adam")
-        upd.add("adam_pack", k_adam, dict(base, update=1, **self._opt_hparams))
         pack = Phase("pack")
         pack.add("pack", k_adam, dict(base, update=0))
-        return {"adam": upd, "pack": pack}
+        self.opt = {"pack": pack}
+        self.set_optimizer(grad_scale=grad_scale)
+        return self.opt
 
     def set_optimizer(self, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale: float = 1.0,
                       data_parallel: bool = False):
@@ -1016,17 +994,19 @@ class LoweredProgram:
                                 data_parallel=data_parallel)
         self._opt_hparams = dict(b1=betas[0], b2=betas[1], eps=eps, wd=weight_decay, grad_scale=grad_scale)
         self.data_parallel = bool(data_parallel)
-        if getattr(self, "_early_adam", None) and (grad_scale != 1.0 or data_parallel):
+        if self._early_adam and (grad_scale != 1.0 or data_parallel):
             raise RuntimeError("the weight updates already run inside the backward: gradient averaging would miss them")
-        for d in getattr(self, "_early_adam", []):  # the side streams' partial updates (batch_wgrads)
+        for d in self._early_adam:  # the side streams' partial updates (batch_wgrads)
             d.update(self._opt_hparams)
         upd = Phase("adam")
         upd.add("adam_pack", k_adam, dict(self._opt_base, update=1, **self._opt_hparams, **self._step_mode()))
         self.opt["adam"] = upd
-        self.set_step_cursor(getattr(self, "_step_cursor", None))
+        self.set_step_cursor(self._step_cursor)
 
-    _step_early = None  # the step-counter launch's args once use_early_step_counter moved it into the forward
     EARLY_STEP_COUNTER = True  # class switch for A/B runs (tools/variant.py)
+    # build_for_stream_buckets rebuilds the program with stream_param_order (models whose module order leaves
+    # stream_buckets no side-stream prefix)
+    REORDER_FOR_STREAM_BUCKETS = False
 
     def _step_mode(self) -> dict:
         return {"t_pre": 1, "inc_step": 0} if self._step_early is not None else {}
@@ -1037,9 +1017,10 @@ class LoweredProgram:
         the step's critical tail (rocprof, Model A: 4 us kernel + its dependency gap; profiles/r6_kernels_*).
         Every Adam launch then uses t = step (AdamArgs::t_pre).  The launch waits for what the side stream's
         first forward launch waits for (after the gather phase, which reads the cursor), and every Adam launch
-        follows it through the forward -> backward joins.  For the step runner (engine/step.py), which always
-        runs the forward before the update; phases run by hand keep the old form.  Idempotent; False (no
-        change) when the forward has no side stream."""
+        follows it through the forward -> backward joins.  The rewrite is permanent for the program: the step
+        runner (engine/step.py) applies it when it wraps a program, and from then on the counter advances in
+        ``fwd_train`` and no longer in the optimizer phase -- also when the phases are run by hand.
+        Idempotent; False (no change) when the forward has no side stream."""
         if self._step_early is not None:
             return True
         if not self.EARLY_STEP_COUNTER:
@@ -1050,7 +1031,7 @@ class LoweredProgram:
             return False
         self._step_early = {"step": self.flat.step.data_ptr()}
         ls.insert(i, Launch("step_inc", k_step_inc, self._step_early, stream=ls[i].stream, waits=tuple(ls[i].waits)))
-        for d in getattr(self, "_early_adam", []):
+        for d in self._early_adam:
             d.update(t_pre=1, inc_step=0)
         self.set_optimizer(**self._opt_kwargs)
         return True
@@ -1061,7 +1042,7 @@ class LoweredProgram:
         launch, or early in the step (use_early_step_counter) -- after every gather block has read it.  None
         detaches it."""
         self._step_cursor = cursor
-        ds = [l.args[0] for l in self.opt["adam"].launches if l.name == "adam_pack"]
+        ds = [l.d for l in self.opt["adam"].launches if l.is_adam]
         if self._step_early is not None:
             ds = [self._step_early]
         for d in ds:
@@ -1082,7 +1063,7 @@ def build_for_stream_buckets(make: Callable, n_buckets: int):
     second time with stream_param_order(), which groups each side stream's parameters.  Returns (program,
     buckets)."""
     prog = make(None)
-    if n_buckets > 1 and getattr(prog, "REORDER_FOR_STREAM_BUCKETS", False):
+    if n_buckets > 1 and prog.REORDER_FOR_STREAM_BUCKETS:
         order = prog.stream_param_order()
         if order is not None:
             del prog

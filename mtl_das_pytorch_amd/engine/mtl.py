@@ -57,6 +57,8 @@ class MTLProgram(LoweredProgram):
 
     def __init__(self, model: MTLNet, batch: int, device, in_hw=(100, 250), loss_weights: Optional[Sequence[float]] = None,
                  sync_world: int = 1):
+        super().__init__()
+        self._rb1_bwd_first = self._rb1_anchor = None  # RB1's first backward launch: the bucket cut candidate
         self.model = model
         self.B = B = batch
         self.T = T = len(model.tasks)

@@ -53,6 +53,59 @@ class Launch:
         self.waits = tuple(waits)
         self.record = record
 
+    # ---- what the launch is: the passes over a launch list ask these, never ``name`` / ``args`` positions ----
+    # (the tuple layout of ``args`` is the k_* adapter's signature without its trailing stream)
+    is_conv_fwd = property(lambda self: self.name == "conv_fwd")
+    is_dgrad = property(lambda self: self.name == "conv_dgrad")
+    is_conv = property(lambda self: self.name in ("conv_fwd", "conv_dgrad"))  # (mode, cfg, G, d)
+    is_wgrad = property(lambda self: self.name == "conv_wgrad")               # (cfg, G, d): one conv's
+    is_wgrad_batch = property(lambda self: self.name == "wgrad_batched")      # (cfg, table, njobs, nblocks, cap)
+    is_tail_fwd = property(lambda self: self.fn is k_tail_fwd)                # (kind, G, blocks, d)
+    # (kind, G, nchunk, d); not the reduce-only "tailpart" pass SyncBN splits off (same kernel, no gradients)
+    is_tail_bwd = property(lambda self: self.name.startswith("tailbwd"))
+    is_finalize = property(lambda self: self.name == "wgrad_finalize")        # owner: its convs (None: all)
+    is_adam = property(lambda self: self.name == "adam_pack")                 # the optimizer phase's (d,)
+    is_early_adam = property(lambda self: self.name == "adam_pack_early")     # a side stream's, in the backward
+    is_cut = property(lambda self: self.name == "cut")                        # gradient-bucket boundary
+    is_join = property(lambda self: self.name == "join_side")                 # side streams -> stream 0
+    is_fork = property(lambda self: self.fn is None and self.name.startswith("fork:"))
+
+    # the tag a fork point was emitted with (Phase.fork_point); "" for any other launch
+    fork_tag = property(lambda self: self.name[len("fork:"):] if self.is_fork else "")
+    # the argument dict (None: a launch whose arguments are a device table or tensors)
+    d = property(lambda self: next((a for a in self.args if isinstance(a, dict)), None))
+    kind = property(lambda self: self.args[0])    # activation kind of a BN-tail launch
+    nchunk = property(lambda self: self.args[2])  # grid of a BN-tail launch (forward: blocks, backward: BN chunks)
+    # tile config of a conv forward / dgrad, of a per-conv or a batched weight gradient
+    cfg = property(lambda self: self.args[1] if self.fn is k_conv else self.args[0])
+
+    @property
+    def G(self) -> int:
+        """Group count (task branches run as one grouped launch); 1 where the kernel has none."""
+        if self.fn is k_conv:
+            return self.args[2]
+        return self.args[1] if self.fn in (k_wgrad, k_tail_fwd, k_tail_bwd) else 1
+
+    def set_cfg(self, cfg: int, d: dict = None):
+        """Point a conv or per-conv weight-gradient launch at tile config ``cfg`` -- the ONE place a config
+        changes: a weight gradient's config also decides its ConvLayer's split plan (slab layout, finalize
+        descriptors), so the owning layer is updated with it.  ``d``: a conv's new argument dict (a config that
+        needs a workspace: ops.functional.conv_workspace writes its pointers into the dict)."""
+        if self.fn is k_conv:
+            mode, _, G, old = self.args
+            self.args = (mode, cfg, G, old if d is None else d)
+        elif self.fn is k_wgrad:
+            if self.owner is not None:
+                self.owner.set_wgrad_cfg(cfg)
+            self.args = (cfg,) + self.args[1:]
+        else:
+            raise TypeError(f"{self.name} has no tile config to set")
+
+    def rewrite(self, name: str, fn: Callable, *args):
+        """Turn this launch object into another launch in place: it keeps its identity (bucket-cut anchors and
+        owner lists refer to it), stream, waits, record and bucket."""
+        self.name, self.fn, self.args = name, fn, args
+
     def __call__(self, st: int, tstream=None):
         if self.fn is None:  # a pseudo-launch that only carries waits / a record (fork point)
             return
@@ -177,6 +230,8 @@ class Phase:
         self.cur_stream = 0      # default stream id for add()
         self.pending_waits = []  # waits attached to the next add() on any stream
         self.alias = {}          # event tag -> tag it is recorded under (after launches were removed)
+        self.ws_keep = {}        # id(launch) -> split-K workspace of its tuned conv config (engine/tune.py)
+        self.keep = ()           # device tensors whose pointers the launches hold (window phases)
 
     def add(self, name, fn, *args, owner=None, stream=None, waits=(), record=None):
         sid = self.cur_stream if stream is None else stream

@@ -87,7 +87,7 @@ class StepRunner:
         self.ext_dp = self.use_graph and allreduce is not None and not self.capture_dp
         self.ext_events = None
         reducing = allreduce is not None and getattr(getattr(allreduce, "ctx", None), "enabled", False)
-        if reducing and any(l.name == "adam_pack_early" for l in program.bwd.launches):
+        if reducing and any(l.is_early_adam for l in program.bwd.launches):
             # an update inside the backward would use local, un-reduced gradients
             raise ValueError("data-parallel step with weight updates inside the backward: call "
                              "set_optimizer(data_parallel=True) before autotune_program")
@@ -95,7 +95,7 @@ class StepRunner:
             program.use_early_step_counter()  # the step counter off the step's tail (every step runs the forward)
         if hasattr(program, "check_sync_bn"):
             program.check_sync_bn()  # every SyncBN collective the program promised is in its launch lists
-        self.buckets = list(getattr(program, "buckets", None) or [(0, program.flat.numel)])
+        self.buckets = list(program.buckets or [(0, program.flat.numel)])
         self.schedule = None  # [nrows][B] batch-index schedule (set_index_schedule)
         self.cursor = None
         self.window = None  # resident-recording inference (set_window_source): (rec, fs, ts, probs, lo, hi)
@@ -134,7 +134,7 @@ class StepRunner:
         # left either behind would skip the first batch
         infer = [self.window_cursor, self.window[3]] if kind == "infer" else []
         return ([f.params, f.grads, f.exp_avg, f.exp_avg_sq, f.bn_mean, f.bn_var, f.bn_nbt, f.step, self.p.metrics,
-                 self.p.confusion, self.p.logp] + list(getattr(self.p, "extra_state", []))
+                 self.p.confusion, self.p.logp] + list(self.p.extra_state)
                 + ([self.cursor] if self.cursor is not None else []) + infer)
 
     def pack_weights(self):

@@ -123,9 +123,8 @@ def autotune_phases(phases: Iterable, cache: Optional[Dict[str, int]] = None, ve
     cache = load_cache() if cache is None else cache
     L = lib()
     for ph in phases:
-        keep = ph.__dict__.setdefault("ws_keep", {})  # split-K workspaces of the chosen LDS configs
         for launch in ph.launches:
-            if launch.name not in ("conv_fwd", "conv_dgrad"):
+            if not launch.is_conv:
                 continue
             mode, cfg, G, d = launch.args
             sig = conv_signature(mode, G, d)
@@ -140,36 +139,34 @@ def autotune_phases(phases: Iterable, cache: Optional[Dict[str, int]] = None, ve
             ws = conv_workspace(mode, cfg, G, d, torch.device("cuda", torch.cuda.current_device()))
             if ws is None:
                 raise RuntimeError(f"cached conv config {cfg} is invalid for {sig}")
-            keep[id(launch)] = ws
-            launch.args = (mode, cfg, G, d)
+            ph.ws_keep[id(launch)] = ws  # split-K workspace of the chosen LDS config
+            launch.set_cfg(cfg)
     for ph in phases:
         for launch in ph.launches:
-            if launch.name != "conv_wgrad" or launch.owner is None:
+            if not launch.is_wgrad or launch.owner is None:
                 continue
             cfg, G, d = launch.args
-            conv = launch.owner
             sig = wgrad_signature(G, d)
             if sig not in cache and not measure:
                 continue
             if sig not in cache:
                 best, best_t = cfg, float("inf")
                 for c in WGRAD_CFGS:
-                    if not conv.wgrad_valid(c):
+                    if not launch.owner.wgrad_valid(c):
                         continue
-                    conv.set_wgrad_cfg(c)
+                    launch.set_cfg(c)
                     t = _time(lambda: L.wgrad(c, G, torch.cuda.current_stream().cuda_stream, d))
                     if t < best_t:
                         best, best_t = c, t
                 cache[sig] = best
                 if verbose:
                     print(f"tuned {sig}: cfg {best} ({best_t * 1e3:.1f} us)", flush=True)
-            conv.set_wgrad_cfg(cache[sig])
-            launch.args = (cache[sig], G, d)
+            launch.set_cfg(cache[sig])
     # BN backward: reduce + apply (grid over pixels, replica atomics) vs the single-launch variant
     # (one block per 8 channels over all pixels) -- the crossover depends on M, C and the sources
     for ph in phases:
         for launch in ph.launches:
-            if not launch.name.startswith("tailbwd"):
+            if not launch.is_tail_bwd:
                 continue
             kind, G, blocks, d = launch.args
             if d.get("fused") in (2, 3):  # statistics from the producers (apply only) / a partial reduce
@@ -230,6 +227,24 @@ def autotune_program(prog, out_path: Optional[str] = None, verbose: bool = False
     return cache
 
 
+def _wgrad_groups(prog) -> tuple:
+    """(per-conv weight-gradient launches, the same grouped by signature, signature -> work of its group)."""
+    wg = [l for l in prog.bwd.launches if l.is_wgrad and l.owner is not None]
+    groups: Dict[str, list] = {}
+    for l in wg:
+        groups.setdefault(wgrad_signature(l.G, l.d), []).append(l)
+
+    def weight(sig):
+        d = groups[sig][0].d
+        return len(groups[sig]) * d["B"] * d["Ho"] * d["Wo"] * d["Npad"] * d["Kpad"]
+    return wg, groups, weight
+
+
+def _big_cfg(conv) -> int:
+    """The large-tile weight-gradient config a conv's shape suits."""
+    return WGRAD_BIG0 + 2 * (conv.Npad > 64) + (conv.Kpad_w > 64)
+
+
 def tune_wgrad_batches(prog, cache: Dict[str, int], verbose: bool = False, passes: int = 1,
                        init_big: bool = False, init_lean=False) -> Dict[str, int]:
     """Choose the weight-gradient configs by the time of the BATCHED launches they end up in.
@@ -246,37 +261,29 @@ def tune_wgrad_batches(prog, cache: Dict[str, int], verbose: bool = False, passe
     stream -- instead of the table's choices.  Must run before batch_wgrads (on the per-conv launches).
     Updates and returns ``cache``."""
     L = lib()
-    wg = [l for l in prog.bwd.launches if l.name == "conv_wgrad" and l.owner is not None]
+    wg, groups, weight = _wgrad_groups(prog)
     if not wg:
         return cache
-    groups: Dict[str, list] = {}
-    for l in wg:
-        groups.setdefault(wgrad_signature(l.args[1], l.args[2]), []).append(l)
-    assign = {sig: ls[0].args[0] for sig, ls in groups.items()}
-    fin = [l for l in prog.bwd.launches if l.name == "wgrad_finalize"]
+    assign = {sig: ls[0].cfg for sig, ls in groups.items()}
+    fin = [l for l in prog.bwd.launches if l.is_finalize]
 
     def cost() -> float:
         for sig, ls in groups.items():
             for l in ls:
-                l.owner.set_wgrad_cfg(assign[sig])
-                l.args = (assign[sig],) + tuple(l.args[1:])
+                l.set_cfg(assign[sig])
         prog.merge_wgrad_cfgs()
         prog.refresh_wgrad_finalize()
-        total, tables = 0.0, []
-        for key in sorted({(l.bucket, l.stream, l.args[0]) for l in wg}):
-            job = [l for l in wg if (l.bucket, l.stream, l.args[0]) == key]
-            raw, nblocks = L.wgrad_table(key[2], [l.args[2] for l in job], [l.args[1] for l in job])
-            t = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(prog.device)
-            tables.append(t)
-            total += _time(lambda c=key[2], t=t, n=len(job), nb=nblocks:
-                           L.wgrad_batched(c, t.data_ptr(), n, nb, torch.cuda.current_stream().cuda_stream, 0))
+        total, n_kept = 0.0, len(prog.keep_alive)
+        for bk, st in sorted({(l.bucket, l.stream) for l in wg}):
+            mine = [l for l in wg if (l.bucket, l.stream) == (bk, st)]
+            for b in prog._batch_stream_wgrads(mine, st, [], "", bk)[1]:
+                cfg, t, n, nb, _ = b.args  # timed on an uncapped grid (one block per virtual block)
+                total += _time(lambda: L.wgrad_batched(cfg, t.data_ptr(), n, nb,
+                                                       torch.cuda.current_stream().cuda_stream, 0))
+        del prog.keep_alive[n_kept:]  # the timed job tables; the launches keep their per-conv form
         for f in fin:
             total += _time(lambda f=f: f.fn(*f.args, torch.cuda.current_stream().cuda_stream))
         return total
-
-    def weight(sig):
-        d = groups[sig][0].args[2]
-        return len(groups[sig]) * d["B"] * d["Ho"] * d["Wo"] * d["Npad"] * d["Kpad"]
 
     t0 = cost()
     if init_lean:  # signatures on their fastest lean-staging config, timed alone (csrc/wgrad_lean.hip); a set of
@@ -289,16 +296,14 @@ def tune_wgrad_batches(prog, cache: Dict[str, int], verbose: bool = False, passe
             for c in range(WGRAD_LEAN0, WGRAD_LEAN0 + WGRAD_LEAN_N):
                 if not all(l.owner.wgrad_valid(c) for l in ls):
                     continue
-                l0.owner.set_wgrad_cfg(c)
-                cand.append((_time(lambda c=c: L.wgrad(c, l0.args[1], torch.cuda.current_stream().cuda_stream,
-                                                       l0.args[2])), c))
-            l0.owner.set_wgrad_cfg(assign[sig])
+                l0.set_cfg(c)
+                cand.append((_time(lambda c=c: L.wgrad(c, l0.G, torch.cuda.current_stream().cuda_stream, l0.d)), c))
+            l0.set_cfg(assign[sig])
             if cand:
                 assign[sig] = min(cand)[1]
     if init_big:
         for sig, ls in groups.items():
-            conv = ls[0].owner
-            c = WGRAD_BIG0 + 2 * (conv.Npad > 64) + (conv.Kpad_w > 64)
+            c = _big_cfg(ls[0].owner)
             if assign[sig] not in WGRAD_PATCH and all(l.owner.wgrad_valid(c) for l in ls):
                 assign[sig] = c
     best = cost()
@@ -341,15 +346,7 @@ def tune_wgrad_in_step(make_prog, X: torch.Tensor, labels: torch.Tensor, cache: 
     returns ``cache``."""
     L = lib()
     base = make_prog()
-    wg = [l for l in base.bwd.launches if l.name == "conv_wgrad" and l.owner is not None]
-    groups: Dict[str, list] = {}
-    for l in wg:
-        groups.setdefault(wgrad_signature(l.args[1], l.args[2]), []).append(l)
-
-    def weight(sig):
-        d = groups[sig][0].args[2]
-        return len(groups[sig]) * d["B"] * d["Ho"] * d["Wo"] * d["Npad"] * d["Kpad"]
-
+    wg, groups, weight = _wgrad_groups(base)
     order = sorted(groups, key=weight, reverse=True)[:top]
     ranked = {}
     for sig in order:  # isolated ranking of the signature's valid configs (first launch of the group)
@@ -358,11 +355,11 @@ def tune_wgrad_in_step(make_prog, X: torch.Tensor, labels: torch.Tensor, cache: 
         conv, res = l.owner, []
         for c in WGRAD_CFGS:
             if all(k.owner.wgrad_valid(c) for k in groups[sig]):
-                conv.set_wgrad_cfg(c)
+                l.set_cfg(c)
                 res.append((_time(lambda c=c: L.wgrad(c, G, torch.cuda.current_stream().cuda_stream, d)), c))
-        conv.set_wgrad_cfg(cfg0)
+        l.set_cfg(cfg0)
         res.sort()
-        big = WGRAD_BIG0 + 2 * (conv.Npad > 64) + (conv.Kpad_w > 64)
+        big = _big_cfg(conv)
         cands = [c for _, c in res[:topk]]
         for c in (big, big - WGRAD_BIG0 + WGRAD_LEANBIG0):  # the large tile and its lean-staging form
             if c in {c2 for _, c2 in res} and c not in cands:
@@ -418,23 +415,23 @@ def tune_wgrad_in_step(make_prog, X: torch.Tensor, labels: torch.Tensor, cache: 
     return cache
 
 
-def step_time_us(prog, X: torch.Tensor, labels: torch.Tensor, reps: int = 100, rounds: int = 3) -> float:
-    """Best-of-``rounds`` mean time of the training step (gather, forward, backward, Adam + re-pack at
-    learning rate 0) captured as one HIP graph; the program's mutable state is restored afterwards."""
-    from .step import StateSnapshot, capture_graph
+def _snapshot(prog):
+    """The program's mutable state (restored after a timing run that trains at learning rate 0)."""
+    from .step import StateSnapshot
     f = prog.flat
-    snap = StateSnapshot([f.params, f.grads, f.exp_avg, f.exp_avg_sq, f.bn_mean, f.bn_var, f.bn_nbt, f.step,
-                          f.lr, prog.metrics, prog.confusion, prog.logp] + list(getattr(prog, "extra_state", [])))
-    f.lr.zero_()
-    prog.opt["pack"].run()
-    idx = torch.arange(prog.B, device=prog.device) % X.shape[0]
-    gather = prog.gather_phase(X, labels, idx, clear=True)
-    fns = [gather.run, prog.fwd_train.run, prog.bwd.run, prog.opt["adam"].run]
+    return StateSnapshot([f.params, f.grads, f.exp_avg, f.exp_avg_sq, f.bn_mean, f.bn_var, f.bn_nbt, f.step,
+                          f.lr, prog.metrics, prog.confusion, prog.logp] + list(prog.extra_state))
+
+
+def _graph_ms(fns, reps: int, rounds: int, warm: int = 1) -> float:
+    """Best-of-``rounds`` mean replay time (ms) of ``fns`` captured as one HIP graph, after one eager pass (the
+    code objects of a new config are loaded before the capture) and ``warm`` replays."""
+    from .step import capture_graph
     for fn_ in fns:
         fn_()
     torch.cuda.synchronize()
-    g, keep = capture_graph(fns)
-    for _ in range(10):
+    g, events = capture_graph(fns)
+    for _ in range(warm):
         g.replay()
     torch.cuda.synchronize()
     best = float("inf")
@@ -445,9 +442,21 @@ def step_time_us(prog, X: torch.Tensor, labels: torch.Tensor, reps: int = 100, r
             g.replay()
         e.record()
         torch.cuda.synchronize()
-        best = min(best, 1e3 * s.elapsed_time(e) / reps)
-    g.reset()
-    del g, keep
+        best = min(best, s.elapsed_time(e) / reps)
+    g.reset()  # release the graph and its executable now (hundreds of captures per tuning run)
+    del g, events
+    return best
+
+
+def step_time_us(prog, X: torch.Tensor, labels: torch.Tensor, reps: int = 100, rounds: int = 3) -> float:
+    """Best-of-``rounds`` mean time of the training step (gather, forward, backward, Adam + re-pack at
+    learning rate 0) captured as one HIP graph; the program's mutable state is restored afterwards."""
+    snap = _snapshot(prog)
+    prog.flat.lr.zero_()
+    prog.opt["pack"].run()
+    idx = torch.arange(prog.B, device=prog.device) % X.shape[0]
+    gather = prog.gather_phase(X, labels, idx, clear=True)
+    best = 1e3 * _graph_ms([gather.run, prog.fwd_train.run, prog.bwd.run, prog.opt["adam"].run], reps, rounds, warm=10)
     snap.restore()
     prog.opt["pack"].run()
     torch.cuda.synchronize()
@@ -492,7 +501,7 @@ def _set_conv_cfg(launch, cfg: int, keep: dict) -> bool:
     if ws is None:
         return False
     keep[id(launch)] = ws
-    launch.args = (mode, cfg, G, dc)
+    launch.set_cfg(cfg, dc)
     return True
 
 
@@ -512,42 +521,20 @@ def tune_in_context(prog, X: torch.Tensor, labels: torch.Tensor, cache: Dict[str
     replayed step gets faster by more than ``margin``; finally the whole tuned set must beat the starting
     choices in ``confirm_rounds`` interleaved re-timings, or it is reverted.  The program's mutable state is
     restored afterwards.  Updates and returns ``cache``."""
-    from .step import StateSnapshot, capture_graph
-    f = prog.flat
-    snap = StateSnapshot([f.params, f.grads, f.exp_avg, f.exp_avg_sq, f.bn_mean, f.bn_var, f.bn_nbt, f.step,
-                          f.lr, prog.metrics, prog.confusion, prog.logp] + list(getattr(prog, "extra_state", [])))
-    f.lr.zero_()
+    snap = _snapshot(prog)
+    prog.flat.lr.zero_()
     idx = torch.arange(prog.B, device=prog.device) % X.shape[0]
     gather = prog.gather_phase(X, labels, idx, clear=True)
     fns = [gather.run, prog.fwd_train.run, prog.bwd.run, prog.opt["adam"].run]
     keep = {}
-    for ph in (prog.fwd_train, prog.bwd):
-        ph.__dict__.setdefault("ws_keep", {})
 
     def step_ms() -> float:
-        for fn_ in fns:  # eager pass: code objects of a new config loaded before capture
-            fn_()
-        torch.cuda.synchronize()
-        g, events = capture_graph(fns)
-        g.replay()
-        torch.cuda.synchronize()
-        best = float("inf")
-        for _ in range(rounds):
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(reps):
-                g.replay()
-            e.record()
-            torch.cuda.synchronize()
-            best = min(best, s.elapsed_time(e) / reps)
-        g.reset()  # release the graph and its executable now (hundreds of captures per tuning run)
-        del g, events
-        return best
+        return _graph_ms(fns, reps, rounds)
 
     groups: Dict[str, list] = {}
     for ph in (prog.fwd_train, prog.bwd):
         for l in ph.launches:
-            if l.name in ("conv_fwd", "conv_dgrad"):
+            if l.is_conv:
                 mode, cfg, G, d = l.args
                 groups.setdefault(conv_signature(mode, G, d), []).append(l)
     order = []
@@ -560,8 +547,8 @@ def tune_in_context(prog, X: torch.Tensor, labels: torch.Tensor, cache: Dict[str
     # the starting choices, for the closing confirmation (every accepted toggle beat the incumbent measured
     # right before it, but many toggles at a small margin can still add up to drift -- round 4 accepted 24
     # changes whose sum was 1.9 % SLOWER)
-    start_cfg = {id(l): l.args[1] for ls in groups.values() for l in ls}
-    start_fused = {id(l): l.args[3].get("fused", 0) for l in prog.bwd.launches if l.name.startswith("tailbwd")}
+    start_cfg = {id(l): l.cfg for ls in groups.values() for l in ls}
+    start_fused = {id(l): l.d.get("fused", 0) for l in prog.bwd.launches if l.is_tail_bwd}
     cache_before = dict(cache)
     base = step_ms()
     t0 = base
@@ -600,7 +587,7 @@ def tune_in_context(prog, X: torch.Tensor, labels: torch.Tensor, cache: Dict[str
     if xcd_pass:
         for _, sig in order:
             ls = groups[sig]
-            cur = ls[0].args[1]
+            cur = ls[0].cfg
             t_inc = step_ms()
             if not all(_set_conv_cfg(l, cur ^ CONV_XCD, keep) for l in ls):
                 for l in ls:
@@ -622,7 +609,7 @@ def tune_in_context(prog, X: torch.Tensor, labels: torch.Tensor, cache: Dict[str
     # autotune_phases, re-decided in the step the same way
     tails: Dict[str, list] = {}
     for l in prog.bwd.launches:
-        if l.name.startswith("tailbwd") and l.args[3].get("fused", 0) in (0, 1):
+        if l.is_tail_bwd and l.d.get("fused", 0) in (0, 1):
             kind, G, blocks, d = l.args
             tails.setdefault(tail_bwd_signature(kind, G, d), []).append(l)
     for sig, ls in (tails.items() if tail_pass else []):
@@ -633,7 +620,7 @@ def tune_in_context(prog, X: torch.Tensor, labels: torch.Tensor, cache: Dict[str
             continue
         t_inc = step_ms()
         for l in ls:
-            l.args[3]["fused"] = alt
+            l.d["fused"] = alt
         t = step_ms()
         if t < t_inc * (1.0 - margin) and step_ms() < t_inc * (1.0 - margin):
             base = t
@@ -644,21 +631,21 @@ def tune_in_context(prog, X: torch.Tensor, labels: torch.Tensor, cache: Dict[str
                 on_change(cache)
         else:
             for l in ls:
-                l.args[3]["fused"] = cur
+                l.d["fused"] = cur
     # closing confirmation: the final choices against the starting ones, interleaved rounds; the tuned set is
     # kept only if it is faster in every round by ``margin`` (else the starting table is restored)
-    changed = [l for ls in groups.values() for l in ls if l.args[1] != start_cfg[id(l)]]
-    ch_tails = [l for l in prog.bwd.launches if l.name.startswith("tailbwd")
-                and l.args[3].get("fused", 0) != start_fused.get(id(l), l.args[3].get("fused", 0))]
+    changed = [l for ls in groups.values() for l in ls if l.cfg != start_cfg[id(l)]]
+    ch_tails = [l for l in prog.bwd.launches if l.is_tail_bwd
+                and l.d.get("fused", 0) != start_fused.get(id(l), l.d.get("fused", 0))]
     if changed or ch_tails:
-        final_cfg = {id(l): l.args[1] for l in changed}
-        final_fused = {id(l): l.args[3].get("fused", 0) for l in ch_tails}
+        final_cfg = {id(l): l.cfg for l in changed}
+        final_fused = {id(l): l.d.get("fused", 0) for l in ch_tails}
 
         def apply(start: bool):
             for l in changed:
                 _set_conv_cfg(l, start_cfg[id(l)] if start else final_cfg[id(l)], keep)
             for l in ch_tails:
-                l.args[3]["fused"] = start_fused[id(l)] if start else final_fused[id(l)]
+                l.d["fused"] = start_fused[id(l)] if start else final_fused[id(l)]
         wins = []
         for _ in range(confirm_rounds):
             apply(True)
@@ -677,7 +664,7 @@ def tune_in_context(prog, X: torch.Tensor, labels: torch.Tensor, cache: Dict[str
                 print(f"in-context tuning: {len(changed)} conv / {len(ch_tails)} tail changes not confirmed "
                       f"against the starting table -- reverted", flush=True)
     for ph in (prog.fwd_train, prog.bwd, prog.fwd_eval):
-        ph.__dict__["ws_keep"].update(keep)
+        ph.ws_keep.update(keep)
     if verbose:
         print(f"in-context tuning: step {t0 * 1e3:.1f} -> {base * 1e3:.1f} us", flush=True)
     snap.restore()

@@ -194,8 +194,7 @@ def _force_big_wgrad(prog):
             c = 32 + i % 4
             i += 1
             if l.owner.wgrad_valid(c):
-                l.owner.set_wgrad_cfg(c)
-                l.args = (c,) + tuple(l.args[1:])
+                l.set_cfg(c)
     prog.refresh_wgrad_finalize()  # the split counts changed with the configs (as autotune_program does)
     return i
 

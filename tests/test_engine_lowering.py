@@ -210,8 +210,7 @@ def test_merge_wgrad_cfgs_caps_batches_per_stream():
     for i, l in enumerate(wg):  # scatter the convs over every config valid for them
         valid = [c for c in cfgs if l.owner.wgrad_valid(c)]
         c = valid[i % len(valid)]
-        l.owner.set_wgrad_cfg(c)
-        l.args = (c,) + tuple(l.args[1:])
+        l.set_cfg(c)
     before = {st: len({l.args[0] for l in wg if l.stream == st}) for st in {l.stream for l in wg}}
     assert max(before.values()) > 3
     assert p.merge_wgrad_cfgs(3) > 0

@@ -62,7 +62,7 @@ def instrumentable(l) -> bool:
         return True
     if l.name.startswith("tail") and not l.name.startswith("tailbatch") and not l.name.startswith("tailbwd"):
         return True  # forward tails (tail_fwd_kernel)
-    return l.name.startswith("tailbwd") and d.get("fused", 0) == 2  # apply-only backward (bnb_apply)
+    return l.is_tail_bwd and d.get("fused", 0) == 2  # apply-only backward (bnb_apply)
 
 
 def phases_of(buf: torch.Tensor):

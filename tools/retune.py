@@ -124,7 +124,7 @@ def main():
                             mode, cfg, G, d = l.args
                             cfg = (cfg | CONV_XCD) if args.xcd_init == "on" else (cfg & ~CONV_XCD)
                             cache[conv_signature(mode, G, d)] = cfg
-                            l.args = (mode, cfg, G, d)
+                            l.set_cfg(cfg)
             ps = args.passes.split(",")
             tune_in_context(prog, X, labels, cache, topk=args.topk, margin=args.margin, reps=args.reps,
                             on_change=lambda c: save_cache(c, args.out),  # progress survives a crash

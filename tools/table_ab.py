@@ -38,9 +38,8 @@ def listing(p):
     out = []
     for tag, ph in (("fwd", p.fwd_train), ("bwd", p.bwd)):
         for l in ph.launches:
-            cfg = l.args[1] if l.name in ("conv_fwd", "conv_dgrad") else (
-                l.args[0] if l.name == "wgrad_batched" else None)
-            d = next((a for a in l.args if isinstance(a, dict)), {})
+            cfg = l.cfg if l.is_conv or l.is_wgrad_batch else None
+            d = l.d or {}
             shape = ",".join(str(d[k]) for k in ("Ho", "Wo", "N", "Cs", "KH", "KW", "H", "W", "C") if k in d)
             out.append((tag, l.stream, l.name, shape, cfg, d.get("fused")))
     return out

@@ -50,8 +50,7 @@ def build(model_type: str, policy: str):
                 continue
             c = big_cfg(l.owner)
             if l.owner.wgrad_valid(c):
-                l.owner.set_wgrad_cfg(c)
-                l.args = (c,) + tuple(l.args[1:])
+                l.set_cfg(c)
     p.merge_wgrad_cfgs()
     p.refresh_wgrad_finalize()
     p.batch_wgrads()
@@ -64,9 +63,9 @@ def measure(p, model_type: str, reps: int):
     step_us = step_time_us(p, X, lab, reps)
     batches = []  # operands hold the last replay's data
     for l in p.bwd.launches:
-        if l.name in ("wgrad_batched", "wgrad_finalize"):
+        if l.is_wgrad_batch or l.is_finalize:
             t = _time(lambda l=l: l.fn(*l.args, torch.cuda.current_stream().cuda_stream))  # the capture stream
-            batches.append((l.name, l.args[0] if l.name == "wgrad_batched" else -1, l.stream, 1e3 * t))
+            batches.append((l.name, l.cfg if l.is_wgrad_batch else -1, l.stream, 1e3 * t))
     return step_us, batches
 
 

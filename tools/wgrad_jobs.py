@@ -41,7 +41,6 @@ def main():
     L = lib()
     st = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
     wg = [l for l in prog.bwd.launches if l.name == "conv_wgrad"]
-    prog.wgrad_tables = []
     total = 0.0
     for s in sorted({l.stream for l in wg}):
         for cfg in sorted({l.args[0] for l in wg if l.stream == s}):

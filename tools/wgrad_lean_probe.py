@@ -66,15 +66,13 @@ def main():
               f"k{dd['KH']}x{dd['KW']} s{dd['sh']}: shipped {t0:5.1f} us, best lean c{cb} {tb:5.1f} us | " + " ".join(row),
               flush=True)
     # batched launches per stream: shipped configs vs every job on its best lean config (one batch per config)
-    prog.wgrad_tables = []
     # the shipped table with every large-tile job (32-35) on its lean-staging twin (44-47): same tiles and M split,
     # only the staging differs -- the throughput comparison of the two staging forms
     twin = {k: (c - WGRAD_BIG0 + WGRAD_LEANBIG0 if WGRAD_BIG0 <= c < WGRAD_BIG0 + 4 else c) for k, c in shipped.items()}
     for label, pick in (("shipped", shipped), ("lean", best), ("leanbig-twins", twin)):
         tot = 0.0
         for l in wg:
-            l.owner.set_wgrad_cfg(pick[id(l)])
-            l.args = (pick[id(l)],) + tuple(l.args[1:])
+            l.set_cfg(pick[id(l)])
         for s in sorted({l.stream for l in wg}):
             for cfg in sorted({l.args[0] for l in wg if l.stream == s}):
                 group = [l for l in wg if l.stream == s and l.args[0] == cfg]
