@@ -134,15 +134,15 @@ def conv_workspace(mode: int, cfg: int, G: int, d: dict, device) -> Optional[tup
 class ConvCall:
     """A prepared convolution launch (packed weights + argument dict); ``run()`` enqueues it again."""
 
-    def __init__(self, mode, cfg, d, out, keep):
-        self.mode, self.cfg, self.d, self.out, self._keep = mode, cfg, d, out, keep
-        ws = conv_workspace(mode, cfg, 1, d, out.device)
+    def __init__(self, mode, cfg, d, out, keep, G=1):
+        self.mode, self.cfg, self.d, self.out, self._keep, self.G = mode, cfg, d, out, keep, G
+        ws = conv_workspace(mode, cfg, G, d, out.device)  # partial tiles and tickets of all G groups
         if ws is None:
             raise ValueError(f"conv config {cfg} cannot run this geometry")
         self._ws = ws
 
     def run(self):
-        lib().conv(self.mode, self.cfg, 1, stream(), self.d)
+        lib().conv(self.mode, self.cfg, self.G, stream(), self.d)
         return self.out
 
 
@@ -189,38 +189,95 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     return prepare_conv2d(x, w, bias, stride, padding, stats, x2, cfg, nol).run()
 
 
-def prepare_conv2d_dgrad(dy, w, in_hw, stride=1, padding=0, cin_stored=None, cfg=None, bn_stats=None) -> ConvCall:
+def _rows(t: torch.Tensor, lead: int, what: str) -> Tuple[int, int]:
+    """(pitch, group stride) of a bf16 ``[(G,) B, H, W, C]`` tensor read as rows of pixels: contiguous, or the
+    column slice of a wider contiguous buffer (pitch = the buffer's channel count).  ``lead``: 1 if the tensor
+    carries the group dimension."""
+    if not t.is_cuda:
+        raise RuntimeError("HIP ops need a GPU tensor")
+    if t.dtype != torch.bfloat16 or t.dim() != 4 + lead or t.stride(-1) != 1:
+        raise ValueError(f"{what}: expected a bf16 [{'G, ' if lead else ''}B, H, W, C] tensor with unit channel stride")
+    ld = t.stride(-2)
+    if t.stride(-3) != t.shape[-2] * ld or t.stride(-4) != t.shape[-3] * t.shape[-2] * ld:
+        raise ValueError(f"{what}: the pixels must be rows of one pitch")
+    return ld, (t.stride(0) if lead else 0)
+
+
+def prepare_conv2d_dgrad(dy, w, in_hw, stride=1, padding=0, cin_stored=None, cfg=None, bn_stats=None, groups=None,
+                         add=None) -> ConvCall:
     """``bn_stats`` (optional): ``(y, bn, part, kind)`` -- the dgrad output is the gradient of
     ``act(BN(y))`` and the epilogue accumulates that BN's backward sums sum(dz), sum(dz*xhat) into rows 0/1
-    of ``part`` ([NREP, 3, C] fp64, zero-initialised); see :func:`bn_tail_backward` ``stats_done``."""
+    of ``part`` ([NREP, 3, C] fp64, zero-initialised); see :func:`bn_tail_backward` ``stats_done``.  Or a dict
+    with those four keys and optionally ``r`` (ADD_RELU: the residual), ``bn2`` (its BN: projection shortcut, row
+    2 of ``part`` receives sum(dz*xhat2)), ``C`` (the tail's channels when the gradient has more: ``y`` / ``r``
+    are ``C`` wide) and ``pgs`` (group stride of ``part``; 0: every group adds into one shared tail, ``y`` /
+    ``r`` then carry no group dimension).
+    ``add``: up to 3 more bf16 gradient sources of the output's shape, summed in the epilogue before its one
+    rounding; each may be a column slice of a wider buffer.
+    ``groups`` = G: ``dy``, ``w``, the sources, ``y`` / ``r`` and the output carry a leading ``[G]`` dimension,
+    ``part`` is ``[G, NREP, 3, C]`` and the BN parameters ``[G, C]`` (:func:`bn_args`)."""
+    G = groups or 1
+    lead = 1 if groups else 0
     _check(dy, torch.bfloat16)
-    B, Ho, Wo, Co = dy.shape
-    _, Ci, KH, KW = w.shape
+    if dy.dim() != 4 + lead or w.dim() != 4 + lead or (lead and (dy.shape[0] != G or w.shape[0] != G)):
+        raise ValueError("dgrad: dy [(G,) B, Ho, Wo, Co] and w [(G,) Co, Ci, KH, KW] expected")
+    B, Ho, Wo, Co = dy.shape[lead:]
+    _, Ci, KH, KW = w.shape[lead:]
     Cs = cin_stored or Ci
     H, W = in_hw
     sh, sw = (stride, stride) if isinstance(stride, int) else stride
     ph, pw = (padding, padding) if isinstance(padding, int) else padding
-    wd = pack_weight_dgrad(w.float(), Cs)
+    if lead:
+        wd = torch.stack([pack_weight_dgrad(w[z].float(), Cs) for z in range(G)])
+    else:
+        wd = pack_weight_dgrad(w.float(), Cs)
     from ..engine import guard
-    dx = guard.alloc((B, H, W, Cs), torch.bfloat16, dy.device, label=f"dgrad out cfg {cfg}")
-    d = {"src": {"p0": ptr(dy), "ld0": Co, "C0": Co, "C1": 0}, "w": ptr(wd), "out": ptr(dx), "ldo": Cs,
-         "B": B, "Hs": Ho, "Ws": Wo, "Ho": H, "Wo": W, "N": Cs, "Npad": wd.shape[0], "Cs": Co, "KH": KH, "KW": KW,
-         "sh": sh, "sw": sw, "ph": ph, "pw": pw, "Kpad": wd.shape[1]}
+    dx = guard.alloc(((G,) if lead else ()) + (B, H, W, Cs), torch.bfloat16, dy.device, label=f"dgrad out cfg {cfg}")
+    d = {"src": {"p0": ptr(dy), "ld0": Co, "C0": Co, "C1": 0, "gs0": B * Ho * Wo * Co if lead else 0},
+         "w": ptr(wd), "wgs": wd.shape[-2] * wd.shape[-1] if lead else 0, "out": ptr(dx), "ldo": Cs,
+         "ogs": B * H * W * Cs if lead else 0,
+         "B": B, "Hs": Ho, "Ws": Wo, "Ho": H, "Wo": W, "N": Cs, "Npad": wd.shape[-2], "Cs": Co, "KH": KH, "KW": KW,
+         "sh": sh, "sw": sw, "ph": ph, "pw": pw, "Kpad": wd.shape[-1]}
     keep = (dy, wd)
+    if add:
+        srcs = []
+        for t in add:
+            if tuple(t.shape) != tuple(dx.shape):
+                raise ValueError("add: every extra gradient source has the output's shape")
+            ld, gs = _rows(t, lead, "add")
+            srcs.append({"p": ptr(t), "ld": ld, "gs": gs})
+        d["add"] = srcs
+        keep = keep + tuple(add)
     if bn_stats is not None:
-        y, bn, part, kind = bn_stats
-        _check(y, torch.bfloat16)
-        if part.dtype != torch.float64 or tuple(y.shape) != (B, H, W, Cs):
+        if not isinstance(bn_stats, dict):
+            y, bn, part, kind = bn_stats
+            bn_stats = {"y": y, "bn": bn, "part": part, "kind": kind}
+        y, bn, part, kind = bn_stats["y"], bn_stats["bn"], bn_stats["part"], bn_stats["kind"]
+        r, bn2, pgs = bn_stats.get("r"), bn_stats.get("bn2"), bn_stats.get("pgs")
+        C = bn_stats.get("C") or Cs
+        ylead = 0 if pgs == 0 else lead  # one shared tail: y / r have no group dimension
+        if part.dtype != torch.float64 or tuple(y.shape[-4:]) != (B, H, W, C) or y.dim() != 4 + ylead:
             raise ValueError("bn_stats: y must be the [B, H, W, C] bf16 BN input and part fp64 [NREP, 3, C]")
-        d["bnb"] = {"y": ptr(y), "ldy": Cs, "bn": bn, "part": ptr(part), "kind": kind}
-        keep = keep + (y, part)
-    return ConvCall(1, _fwd_cfg(Cs, B * H * W) if cfg is None else cfg, d, dx, keep)
+        ldy, ygs = _rows(y, ylead, "bn_stats y")
+        b = {"y": ptr(y), "ldy": ldy, "ygs": ygs, "bn": bn, "part": ptr(part), "kind": kind, "C": C}
+        if pgs is not None:
+            b["pgs"] = pgs
+        if r is not None:
+            if tuple(r.shape) != tuple(y.shape):
+                raise ValueError("bn_stats: r must have y's shape")
+            ldr, rgs = _rows(r, ylead, "bn_stats r")
+            b.update({"r": ptr(r), "ldr": ldr, "rgs": rgs})
+        if bn2 is not None:
+            b["bn2"] = bn2
+        d["bnb"] = b
+        keep = keep + (y, part, r)
+    return ConvCall(1, _fwd_cfg(Cs, B * H * W) if cfg is None else cfg, d, dx, keep, G)
 
 
 def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, in_hw: Tuple[int, int], stride=1, padding=0,
-                 cin_stored: Optional[int] = None, cfg: Optional[int] = None, bn_stats=None):
+                 cin_stored: Optional[int] = None, cfg: Optional[int] = None, bn_stats=None, groups=None, add=None):
     """Gradient w.r.t. the NHWC input: bf16 ``[B, H, W, Cin_stored]`` (fp32 accumulation, one rounding)."""
-    return prepare_conv2d_dgrad(dy, w, in_hw, stride, padding, cin_stored, cfg, bn_stats).run()
+    return prepare_conv2d_dgrad(dy, w, in_hw, stride, padding, cin_stored, cfg, bn_stats, groups, add).run()
 
 
 WGRAD_TILES = {0: (16, 32, 128), 1: (32, 32, 128), 2: (32, 64, 64), 3: (64, 64, 64), 4: (16, 64, 128),
@@ -338,30 +395,54 @@ def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, w_shape, stride=1, padding=0
 ACT_NONE, ACT_RELU, ACT_SIGMOID, SIGMUL, ADD_RELU, POOL_RELU = range(6)
 
 
-def bn_args(stats, gamma, beta, run_mean, run_var, nbt, count, eps=1e-5, momentum=0.1, training=True):
+def bn_args(stats, gamma, beta, run_mean, run_var, nbt, count, eps=1e-5, momentum=0.1, training=True,
+            consts=None, nrep=None, pnrep=None):
     """Kernel BN descriptor.  The dict keeps references to the tensors it points at (``_keep``) so that
-    they cannot be freed while a launch may still use them."""
+    they cannot be freed while a launch may still use them.  Grouped launches: parameters ``[G, C]``, ``stats``
+    ``[G, NREP, 2, C]``.  ``consts`` ([G, 4, C] fp32: scale, shift, mean, invstd): the batch constants the
+    forward tail publishes and every backward kernel reads instead of the replicas; ``nrep`` / ``pnrep``:
+    replicas in use of the forward sums / of the backward partial sums (powers of two <= NREP)."""
     if stats.dtype != torch.float64:
         raise TypeError("BN statistic replicas are fp64 ([NREP, 2, C])")
-    return {"_keep": (stats, gamma, beta, run_mean, run_var, nbt),"stats": ptr(stats), "gamma": ptr(gamma), "beta": ptr(beta), "run_mean": ptr(run_mean),
-            "run_var": ptr(run_var), "nbt": ptr(nbt) if nbt is not None else 0, "pstride": 0, "C": gamma.numel(),
-            "count": count, "eps": eps, "momentum": momentum, "training": 1 if training else 0}
+    if gamma.dim() == 2 and not all(t.is_contiguous() and t.shape == gamma.shape for t in (gamma, beta, run_mean, run_var)):
+        raise ValueError("grouped BN parameters must be contiguous [G, C]")
+    d = {"_keep": (stats, gamma, beta, run_mean, run_var, nbt, consts), "stats": ptr(stats), "gamma": ptr(gamma),
+         "beta": ptr(beta), "run_mean": ptr(run_mean),
+         "run_var": ptr(run_var), "nbt": ptr(nbt) if nbt is not None else 0,
+         "pstride": gamma.shape[-1] if gamma.dim() == 2 else 0, "C": gamma.shape[-1],
+         "count": count, "eps": eps, "momentum": momentum, "training": 1 if training else 0}
+    if consts is not None:
+        _check(consts, torch.float32)
+        if tuple(consts.shape[-2:]) != (4, gamma.shape[-1]):
+            raise ValueError("consts must be [G, 4, C]")
+        d["consts"] = ptr(consts)
+    if nrep is not None:
+        d["nrep"] = nrep
+    if pnrep is not None:
+        d["pnrep"] = pnrep
+    return d
 
 
 def bn_tail(kind: int, y: torch.Tensor, bn: dict, r: Optional[torch.Tensor] = None, bn2: Optional[dict] = None,
-            blocks: int = 64):
-    """Fused BN(+act/+mul/+residual/+pool) forward on NHWC bf16 ``y``; returns the bf16 output."""
-    B, H, W, C = y.shape
+            blocks: int = 64, groups: Optional[int] = None):
+    """Fused BN(+act/+mul/+residual/+pool) forward on NHWC bf16 ``y``; returns the bf16 output.  ``groups`` = G:
+    ``y`` / ``r`` and the output carry a leading ``[G]`` dimension (BN parameters ``[G, C]``)."""
+    lead = 1 if groups else 0
+    B, H, W, C = y.shape[lead:]
+    lshape = tuple(y.shape[:lead])
     if kind == POOL_RELU:
-        out = torch.empty(B, (H + 1) // 2, (W + 1) // 2, C, device=y.device, dtype=torch.bfloat16)
+        out = torch.empty(lshape + (B, (H + 1) // 2, (W + 1) // 2, C), device=y.device, dtype=torch.bfloat16)
     else:
-        out = torch.empty_like(y)
-    d = {"y": ptr(y), "ldy": C, "bn": bn, "out": ptr(out), "ldo": C, "B": B, "H": H, "W": W, "C": C}
+        out = torch.empty(tuple(y.shape), device=y.device, dtype=torch.bfloat16)
+    ldy, ygs = _rows(y, lead, "y")
+    d = {"y": ptr(y), "ldy": ldy, "ygs": ygs, "bn": bn, "out": ptr(out), "ldo": C,
+         "ogs": out[0].numel() if lead else 0, "B": B, "H": H, "W": W, "C": C}
     if r is not None:
-        d.update({"r": ptr(r), "ldr": r.shape[-1]})
+        ldr, rgs = _rows(r, lead, "r")
+        d.update({"r": ptr(r), "ldr": ldr, "rgs": rgs})
     if bn2 is not None:
         d["bn2"] = bn2
-    lib().tail_fwd(kind, 1, blocks, stream(), d)
+    lib().tail_fwd(kind, groups or 1, blocks, stream(), d)
     return out
 
 
@@ -389,39 +470,74 @@ def bnb_plan(M: int, C: int, G: int = 1, target_blocks: int = 1024):
 
 def bn_tail_backward(kind: int, y: torch.Tensor, bn: dict, grads: Sequence[torch.Tensor], dgamma, dbeta,
                      r: Optional[torch.Tensor] = None, bn2: Optional[dict] = None, dgamma2=None, dbeta2=None,
-                     fused: bool = False, store_dz: bool = False, part: Optional[torch.Tensor] = None):
+                     fused=False, store_dz: bool = False, part: Optional[torch.Tensor] = None,
+                     gscale: float = 1.0, groups: Optional[int] = None, out: Optional[dict] = None):
     """Returns ``(dy bf16, side bf16 | None, dy2 bf16 | None)``; writes dgamma/dbeta (and 2) in place.
-    ``grads``: the upstream gradient sources (bf16, as the engine stores them; other dtypes are rounded);
-    ``fused``: single-launch variant (block per 8 channels over all pixels) instead of reduce + apply;
+    ``grads``: the upstream gradient sources (bf16, as the engine stores them; other dtypes are rounded), each
+    possibly a column slice of a wider buffer;
+    ``fused``: 1 / True = single-launch variant (block per 8 channels over all pixels) instead of reduce + apply;
+    3 = reduce only: the statistics of ``grads`` (a subset of the tail's sources) are added into ``part``, nothing
+    else is written and ``(None, None, None)`` is returned (dgamma / dbeta are not used);
     ``store_dz``: the reduce stores dz and the apply reads it instead of recomputing it;
-    ``part``: the statistics were already accumulated (by a dgrad with ``bn_stats``): apply pass only."""
-    B, H, W, C = y.shape
-    nchunk, chunk_px = bnb_plan(B * H * W, C)
+    ``part``: the statistics were already accumulated (by a dgrad with ``bn_stats``, by ``fused=3`` launches):
+    apply pass only (``fused=2``);
+    ``gscale``: factor on the dgamma / dbeta the apply writes;
+    ``groups`` = G: every tensor carries a leading ``[G]`` dimension (``part`` [G, NREP, 3, C], parameters and
+    their gradients [G, C]);
+    ``out``: preallocated contiguous bf16 outputs of y's shape to write instead of new ones (keys ``dy``, ``side``,
+    ``dy2``)."""
+    G = groups or 1
+    lead = 1 if groups else 0
+    B, H, W, C = y.shape[lead:]
+    lshape = tuple(y.shape[:lead])
+    nchunk, chunk_px = bnb_plan(B * H * W, C, G)
     mode = int(fused)
-    if part is not None:
+    if mode == 3:
+        if part is None:
+            raise ValueError("fused=3 adds the sources' statistics into part")
+    elif part is not None:
         mode = 2
     else:
-        part = torch.zeros(NREP, 3, C, device=y.device, dtype=torch.float64)
-    dy = torch.empty_like(y)
-    grads = [_grad(g) for g in grads]
-    d = {"y": ptr(y), "ldy": C, "bn": bn, "B": B, "H": H, "W": W, "C": C,
-         "g": [(ptr(g), 0, g.shape[-1]) for g in grads], "part": ptr(part), "chunk_px": chunk_px,
-         "dy": ptr(dy), "ldd": C, "dgamma": ptr(dgamma), "dbeta": ptr(dbeta), "fused": mode}
+        part = torch.zeros(lshape + (NREP, 3, C), device=y.device, dtype=torch.float64)
+    grads = [g if (g.is_cuda and g.dtype == torch.bfloat16 and g.stride(-1) == 1) else _grad(g) for g in grads]
+    ldy, ygs = _rows(y, lead, "y")
+    d = {"y": ptr(y), "ldy": ldy, "ygs": ygs, "bn": bn, "B": B, "H": H, "W": W, "C": C,
+         "g": [(ptr(g),) + _rows(g, lead, "grads")[::-1] for g in grads], "part": ptr(part), "chunk_px": chunk_px,
+         "fused": mode, "gscale": gscale}
+    if r is not None:
+        ldr, rgs = _rows(r, lead, "r")
+        d.update({"r": ptr(r), "ldr": ldr, "rgs": rgs})
+    if bn2 is not None:
+        d["bn2"] = bn2
+    if mode == 3:
+        lib().tail_bwd(kind, G, nchunk, stream(), d)
+        return None, None, None
+    px = B * H * W * C
+
+    def _out(name):
+        t = (out or {}).get(name)
+        if t is None:
+            return torch.empty(tuple(y.shape), device=y.device, dtype=torch.bfloat16)
+        _check(t, torch.bfloat16)
+        if t.shape != y.shape:
+            raise ValueError(f"out[{name!r}] must have y's shape")
+        return t
+    dy = _out("dy")
+    d.update({"dy": ptr(dy), "ldd": C, "dgs": px if lead else 0, "dgamma": ptr(dgamma), "dbeta": ptr(dbeta),
+              "pgs": C if lead else 0})
     dzbuf = None
     if store_dz:
-        dzbuf = torch.empty(B, H, W, C, device=y.device, dtype=torch.bfloat16)
-        d.update({"dzbuf": ptr(dzbuf), "lddz": C})
+        dzbuf = torch.empty(tuple(y.shape), device=y.device, dtype=torch.bfloat16)
+        d.update({"dzbuf": ptr(dzbuf), "lddz": C, "dzgs": px if lead else 0})
     side = dy2 = None
-    if r is not None:
-        d.update({"r": ptr(r), "ldr": r.shape[-1]})
     if kind in (SIGMUL,) or (kind == ADD_RELU and bn2 is None):
-        side = torch.empty(B, H, W, C, device=y.device, dtype=torch.bfloat16)
-        d.update({"side": ptr(side), "lds": C})
+        side = _out("side")
+        d.update({"side": ptr(side), "lds": C, "sgs": px if lead else 0})
     if bn2 is not None:
-        dy2 = torch.empty_like(y)
-        d.update({"bn2": bn2, "dy2": ptr(dy2), "ldd2": C, "dgamma2": ptr(dgamma2),
+        dy2 = _out("dy2")
+        d.update({"dy2": ptr(dy2), "ldd2": C, "d2gs": px if lead else 0, "dgamma2": ptr(dgamma2),
                   "dbeta2": ptr(dbeta2)})
-    lib().tail_bwd(kind, 1, nchunk, stream(), d)
+    lib().tail_bwd(kind, G, nchunk, stream(), d)
     return dy, side, dy2
 
 
