@@ -155,28 +155,61 @@ class WgradCall:
         return self.post(self.slab)
 
 
-def prepare_conv2d(x, w, bias=None, stride=1, padding=0, stats=None, x2=None, cfg=None, nol=None) -> ConvCall:
+def prepare_conv2d(x, w, bias=None, stride=1, padding=0, stats=None, x2=None, cfg=None, nol=None, groups=None,
+                   out=None, stats_nrep=None) -> ConvCall:
+    """The forward launch of :func:`conv2d`.  ``x`` / ``x2`` may each be the column slice of a wider buffer (a pitched
+    input).  ``out``: the bf16 output to write instead of a new one, possibly the column slice of a wider (concat)
+    buffer.  ``stats_nrep``: replica rows in use of ``stats`` (a launch adds into row block % stats_nrep).
+    ``groups`` = G: ``x``, ``x2``, ``w``, ``out`` carry a leading ``[G]`` dimension (the groups of ``x`` / ``out`` one
+    stride apart), ``bias`` is ``[G, Co]`` and ``stats`` ``[G, NREP, 2, Co]``."""
+    G = groups or 1
+    lead = 1 if groups else 0
     if stats is not None and stats.dtype != torch.float64:
         raise TypeError("BN statistic replicas are fp64 ([NREP, 2, Co])")
-    _check(x, torch.bfloat16)
+    if not x.is_cuda:
+        raise RuntimeError("HIP ops need a GPU tensor")
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"expected {torch.bfloat16}, got {x.dtype}")
+    if x.dim() != 4 + lead or w.dim() != 4 + lead or (lead and (x.shape[0] != G or w.shape[0] != G)):
+        raise ValueError("conv: x [(G,) B, H, W, C] and w [(G,) Co, Ci, KH, KW] expected")
+    ld0, gs0 = _rows(x, lead, "x")
+    C0 = x.shape[-1]
     C1 = x2.shape[-1] if x2 is not None else 0
-    Cs = x.shape[-1] + C1
-    B, H, W, Co, Ci, KH, KW, sh, sw, ph, pw, Ho, Wo = _geom(x.shape, w.shape, stride, padding)
+    Cs = C0 + C1
+    B, H, W, Co, Ci, KH, KW, sh, sw, ph, pw, Ho, Wo = _geom(x.shape[lead:], w.shape[lead:], stride, padding)
     if Ci > Cs:
         raise ValueError("weight has more input channels than the input")
-    wf = pack_weight_fwd(w.float(), Cs)
+    if lead:
+        wf = torch.stack([pack_weight_fwd(w[z].float(), Cs) for z in range(G)])
+    else:
+        wf = pack_weight_fwd(w.float(), Cs)
     from ..engine import guard
-    y = guard.alloc((B, Ho, Wo, Co), torch.bfloat16, x.device, label=f"conv out cfg {cfg}")
-    src = {"p0": ptr(x), "ld0": x.shape[-1], "C0": x.shape[-1], "C1": C1}
+    oshape = tuple(x.shape[:lead]) + (B, Ho, Wo, Co)
+    if out is None:
+        y = guard.alloc(oshape, torch.bfloat16, x.device, label=f"conv out cfg {cfg}")
+    else:
+        y = out
+        if tuple(y.shape) != oshape:
+            raise ValueError(f"out must be {oshape}")
+    ldo, ogs = _rows(y, lead, "out")
+    src = {"p0": ptr(x), "ld0": ld0, "gs0": gs0, "C0": C0, "C1": C1}
     if x2 is not None:
-        _check(x2, torch.bfloat16)
-        src.update({"p1": ptr(x2), "ld1": C1})
-    d = {"src": src, "w": ptr(wf), "bias": ptr(bias) if bias is not None else 0, "out": ptr(y), "ldo": Co,
+        if tuple(x2.shape[:-1]) != tuple(x.shape[:-1]):
+            raise ValueError("x2 must have x's pixels")
+        ld1, gs1 = _rows(x2, lead, "x2")
+        src.update({"p1": ptr(x2), "ld1": ld1, "gs1": gs1})
+    if bias is not None and lead and tuple(bias.shape) != (G, Co):
+        raise ValueError("grouped bias must be [G, Co]")
+    d = {"src": src, "w": ptr(wf), "wgs": wf.shape[-2] * wf.shape[-1] if lead else 0,
+         "bias": ptr(bias) if bias is not None else 0, "bgs": Co if lead else 0, "out": ptr(y), "ldo": ldo, "ogs": ogs,
          "stats": ptr(stats) if stats is not None else 0, "B": B, "Hs": H, "Ws": W, "Ho": Ho, "Wo": Wo, "N": Co,
-         "Npad": wf.shape[0], "Cs": Cs, "KH": KH, "KW": KW, "sh": sh, "sw": sw, "ph": ph, "pw": pw, "Kpad": wf.shape[1]}
+         "Npad": wf.shape[-2], "Cs": Cs, "KH": KH, "KW": KW, "sh": sh, "sw": sw, "ph": ph, "pw": pw,
+         "Kpad": wf.shape[-1]}
+    if stats_nrep is not None:
+        d["stats_nrep"] = stats_nrep
     if nol is not None:  # (bn dict of x's BN, kind): x is a pre-BN y, the operand is act(BN(x)) on load
         d["nol"] = {"bn": nol[0], "kind": nol[1]}
-    return ConvCall(0, _fwd_cfg(Co, B * Ho * Wo) if cfg is None else cfg, d, y, (x, x2, wf, bias, stats, nol))
+    return ConvCall(0, _fwd_cfg(Co, B * Ho * Wo) if cfg is None else cfg, d, y, (x, x2, wf, bias, stats, nol), G)
 
 
 def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1, padding=0,
@@ -396,18 +429,20 @@ ACT_NONE, ACT_RELU, ACT_SIGMOID, SIGMUL, ADD_RELU, POOL_RELU = range(6)
 
 
 def bn_args(stats, gamma, beta, run_mean, run_var, nbt, count, eps=1e-5, momentum=0.1, training=True,
-            consts=None, nrep=None, pnrep=None):
+            consts=None, nrep=None, pnrep=None, sld=None, coff=0):
     """Kernel BN descriptor.  The dict keeps references to the tensors it points at (``_keep``) so that
     they cannot be freed while a launch may still use them.  Grouped launches: parameters ``[G, C]``, ``stats``
     ``[G, NREP, 2, C]``.  ``consts`` ([G, 4, C] fp32: scale, shift, mean, invstd): the batch constants the
     forward tail publishes and every backward kernel reads instead of the replicas; ``nrep`` / ``pnrep``:
-    replicas in use of the forward sums / of the backward partial sums (powers of two <= NREP)."""
+    replicas in use of the forward sums / of the backward partial sums (powers of two <= NREP).  ``sld`` / ``coff``:
+    this BN's channels are columns [coff, coff + C) of replica rows ``sld`` wide (``stats`` [G, NREP, 2, sld]: the
+    combined rows of a conv whose output channels feed several BNs)."""
     if stats.dtype != torch.float64:
         raise TypeError("BN statistic replicas are fp64 ([NREP, 2, C])")
     if gamma.dim() == 2 and not all(t.is_contiguous() and t.shape == gamma.shape for t in (gamma, beta, run_mean, run_var)):
         raise ValueError("grouped BN parameters must be contiguous [G, C]")
-    d = {"_keep": (stats, gamma, beta, run_mean, run_var, nbt, consts), "stats": ptr(stats), "gamma": ptr(gamma),
-         "beta": ptr(beta), "run_mean": ptr(run_mean),
+    d = {"_keep": (stats, gamma, beta, run_mean, run_var, nbt, consts), "stats": ptr(stats, coff),
+         "gamma": ptr(gamma), "beta": ptr(beta), "run_mean": ptr(run_mean),
          "run_var": ptr(run_var), "nbt": ptr(nbt) if nbt is not None else 0,
          "pstride": gamma.shape[-1] if gamma.dim() == 2 else 0, "C": gamma.shape[-1],
          "count": count, "eps": eps, "momentum": momentum, "training": 1 if training else 0}
@@ -420,28 +455,39 @@ def bn_args(stats, gamma, beta, run_mean, run_var, nbt, count, eps=1e-5, momentu
         d["nrep"] = nrep
     if pnrep is not None:
         d["pnrep"] = pnrep
+    if sld is not None:
+        d["sld"] = sld
     return d
 
 
-def bn_tail(kind: int, y: torch.Tensor, bn: dict, r: Optional[torch.Tensor] = None, bn2: Optional[dict] = None,
-            blocks: int = 64, groups: Optional[int] = None):
-    """Fused BN(+act/+mul/+residual/+pool) forward on NHWC bf16 ``y``; returns the bf16 output.  ``groups`` = G:
-    ``y`` / ``r`` and the output carry a leading ``[G]`` dimension (BN parameters ``[G, C]``)."""
+def tail_fwd_args(kind: int, y: torch.Tensor, bn: dict, r: Optional[torch.Tensor] = None, bn2: Optional[dict] = None,
+                  groups: Optional[int] = None, out: Optional[torch.Tensor] = None):
+    """(argument dict, output) of a forward tail launch (:func:`bn_tail`; a job of ``lib().tail_table``)."""
     lead = 1 if groups else 0
     B, H, W, C = y.shape[lead:]
-    lshape = tuple(y.shape[:lead])
-    if kind == POOL_RELU:
-        out = torch.empty(lshape + (B, (H + 1) // 2, (W + 1) // 2, C), device=y.device, dtype=torch.bfloat16)
-    else:
-        out = torch.empty(tuple(y.shape), device=y.device, dtype=torch.bfloat16)
+    oshape = tuple(y.shape[:lead]) + ((B, (H + 1) // 2, (W + 1) // 2, C) if kind == POOL_RELU else (B, H, W, C))
+    if out is None:
+        out = torch.empty(oshape, device=y.device, dtype=torch.bfloat16)
+    elif tuple(out.shape) != oshape:
+        raise ValueError(f"out must be {oshape}")
     ldy, ygs = _rows(y, lead, "y")
-    d = {"y": ptr(y), "ldy": ldy, "ygs": ygs, "bn": bn, "out": ptr(out), "ldo": C,
-         "ogs": out[0].numel() if lead else 0, "B": B, "H": H, "W": W, "C": C}
+    ldo, ogs = _rows(out, lead, "out")
+    d = {"y": ptr(y), "ldy": ldy, "ygs": ygs, "bn": bn, "out": ptr(out), "ldo": ldo,
+         "ogs": ogs, "B": B, "H": H, "W": W, "C": C}
     if r is not None:
         ldr, rgs = _rows(r, lead, "r")
         d.update({"r": ptr(r), "ldr": ldr, "rgs": rgs})
     if bn2 is not None:
         d["bn2"] = bn2
+    return d, out
+
+
+def bn_tail(kind: int, y: torch.Tensor, bn: dict, r: Optional[torch.Tensor] = None, bn2: Optional[dict] = None,
+            blocks: int = 64, groups: Optional[int] = None, out: Optional[torch.Tensor] = None):
+    """Fused BN(+act/+mul/+residual/+pool) forward on NHWC bf16 ``y``; returns the bf16 output.  ``groups`` = G:
+    ``y`` / ``r`` and the output carry a leading ``[G]`` dimension (BN parameters ``[G, C]``).  ``y``, ``r`` and
+    ``out`` (the output to write instead of a new one) may each be the column slice of a wider buffer."""
+    d, out = tail_fwd_args(kind, y, bn, r, bn2, groups, out)
     lib().tail_fwd(kind, groups or 1, blocks, stream(), d)
     return out
 
