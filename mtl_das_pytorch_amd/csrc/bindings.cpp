@@ -348,6 +348,47 @@ void gather_batch(int64_t X, int64_t idx, int64_t lab, int lab_w, int64_t out, i
         "gather_batch");
 }
 
+// gather_batch with SNR noise (augment.hip): the gather's arguments and the noise inputs in one dict
+void gather_batch_noise(int64_t stream, py::dict d) {
+  const int64_t cursor = I(d, "cursor");
+  const int nrows = (int)I(d, "nrows");
+  if (cursor && nrows <= 0) throw std::runtime_error("gather_batch_noise: a schedule cursor needs its row count");
+  ZeroRanges z{};
+  py::list zero = d.contains("zero") ? d["zero"].cast<py::list>() : py::list();
+  if (zero.size() > 4) throw std::runtime_error("gather_batch_noise: at most 4 zero ranges");
+  for (size_t i = 0; i < zero.size(); ++i) {
+    auto t = zero[i].cast<py::tuple>();
+    const int64_t ptr = t[0].cast<int64_t>(), bytes = t[1].cast<int64_t>();
+    if (ptr % 16 || bytes % 16 || bytes < 0)
+      throw std::runtime_error("gather_batch_noise: zero range not 16-byte aligned");
+    z.p[i] = reinterpret_cast<uint4*>(static_cast<intptr_t>(ptr));
+    z.n16[i] = bytes / 16;
+  }
+  z.n = (int)zero.size();
+  NoiseArgs nz{};
+  nz.power = P<const float>(d, "power"); nz.snr = P<const float>(d, "snr"); nz.draw = P<const int64_t>(d, "draw");
+  // the 64-bit seed as two 32-bit words (a Python int above 2^63 does not fit the dict's int64 values)
+  nz.seed = ((uint64_t)(uint32_t)I(d, "seed_hi") << 32) | (uint64_t)(uint32_t)I(d, "seed_lo");
+  nz.stream = (int)I(d, "noise_stream");
+  nz.dbg = P<float>(d, "dbg");
+  check(launch_gather_batch_noise(P<const float>(d, "X"), P<const int64_t>(d, "idx"), P<const int64_t>(d, "lab"),
+                                  (int)I(d, "lab_w"), P<bf16_t>(d, "out"), P<int64_t>(d, "lab_out"), (int)I(d, "B"),
+                                  (int)I(d, "Cin"), (int)I(d, "H"), (int)I(d, "W"), (int)I(d, "taps"),
+                                  (int)I(d, "off"), z, reinterpret_cast<const int64_t*>(static_cast<intptr_t>(cursor)),
+                                  nrows, nz, S(stream)),
+        "gather_batch_noise");
+}
+
+void sample_power(int64_t X, int64_t power, int64_t planes, int HW, int64_t stream) {
+  check(launch_sample_power(reinterpret_cast<const float*>(static_cast<intptr_t>(X)),
+                            reinterpret_cast<float*>(static_cast<intptr_t>(power)), planes, HW, S(stream)),
+        "sample_power");
+}
+
+void noise_advance(int64_t draw, int64_t stream) {
+  check(launch_noise_advance(reinterpret_cast<int64_t*>(static_cast<intptr_t>(draw)), S(stream)), "noise_advance");
+}
+
 WindowArgs parse_window(const py::dict& d) {
   WindowArgs a{};
   a.rec = P<const float>(d, "rec"); a.fs = P<const int>(d, "fs"); a.ts = P<const int>(d, "ts");
@@ -476,6 +517,9 @@ PYBIND11_MODULE(_mda_hip, m) {
         py::arg("lab_out"), py::arg("B"), py::arg("Cin"), py::arg("H"), py::arg("W"), py::arg("stream"),
         py::arg("taps") = 0, py::arg("off") = 0, py::arg("zero") = py::list(), py::arg("cursor") = 0,
         py::arg("nrows") = 0);
+  m.def("gather_batch_noise", &gather_batch_noise);
+  m.def("sample_power", &sample_power);
+  m.def("noise_advance", &noise_advance);
   m.def("pool3", &pool3);
   m.def("gather_windows", &gather_windows);
   m.def("window_probs", &window_probs);

@@ -310,6 +310,23 @@ int launch_gather_batch(const float* X, const int64_t* idx, const int64_t* lab, 
                         int64_t* lab_out, int B, int Cin, int H, int W, int taps, int off, const ZeroRanges& zero,
                         const int64_t* cursor, int nrows,
                         hipStream_t st);
+// augment.hip: SNR noise injected by the batch gather (definition: data/noise.py).  Every level a run may change
+// is a device value, so a captured step never needs re-capture.
+struct NoiseArgs {
+  const float* power;    // [N][Cin] mean power of each clean plane of the bound set (launch_sample_power)
+  const float* snr;      // device (lo, hi) in dB: lo == hi is a fixed level, otherwise a per-sample uniform draw
+  const int64_t* draw;   // device draw number (training: advanced once per step by launch_noise_advance)
+  uint64_t seed;         // Philox key
+  int stream;            // stream id of the Gaussian: 0 training, 2 evaluation (1 is the training SNR draw)
+  float* dbg;            // test hook (null in the engine): the unrounded fp32 noisy values [B][Cin][H][W]
+};
+int launch_sample_power(const float* X, float* power, int64_t planes, int HW, hipStream_t st);
+// launch_gather_batch with bf16(x + sigma * g) for every real element; -2 on its limits or a null noise input
+int launch_gather_batch_noise(const float* X, const int64_t* idx, const int64_t* lab, int lab_w, bf16_t* out,
+                              int64_t* lab_out, int B, int Cin, int H, int W, int taps, int off,
+                              const ZeroRanges& zero, const int64_t* cursor, int nrows, const NoiseArgs& noise,
+                              hipStream_t st);
+int launch_noise_advance(int64_t* draw, hipStream_t st);
 int launch_pool3(int is_max, int backward, const PoolArgs& a, hipStream_t st);
 // window.hip: resident-recording inference -- windows cut on the device, probabilities into a resident table,
 // overlapping windows averaged into a cell map

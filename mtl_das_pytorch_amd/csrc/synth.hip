@@ -14,28 +14,11 @@
 // The reference reads field recordings from .mat files (dataset_preparation.py:300-344) and has no
 // generator; this replaces its data source for benchmarks and tests (no network for the real dataset).
 #include "kernels.h"
+#include "philox.h"
 
 namespace mda {
 
 namespace {
-
-constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;
-constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
-
-DEV uint4 philox4x32_10(uint4 ctr, uint2 key) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(PHILOX_M0, ctr.x), lo0 = PHILOX_M0 * ctr.x;
-    const uint32_t hi1 = __umulhi(PHILOX_M1, ctr.z), lo1 = PHILOX_M1 * ctr.z;
-    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-    key.x += PHILOX_W0;
-    key.y += PHILOX_W1;
-  }
-  return ctr;
-}
-
-// uniform in (0, 1]: never 0, so log() is finite
-DEV float u01(uint32_t x) { return ((float)(x >> 8) + 1.f) * (1.f / 16777216.f); }
 
 DEV float linspace01(int i, int n) {  // torch.linspace(0, 1, n)[i] (symmetric evaluation from both ends)
   if (n == 1) return 0.f;

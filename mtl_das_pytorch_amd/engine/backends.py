@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..data.noise import EVAL_SEED, noisy_rows, parse_snr_range
 from ..models import decode_joint, model_tasks
 from ..parallel.dist import (DistContext, FlatGradAllReducer, average_, broadcast_module_state, calibrate_allreduce,
                              sum_)
@@ -57,6 +58,7 @@ class Backend:
     def set_lr(self, lr: float): ...
     def train_batch(self, idx: torch.Tensor): ...
     def eval_batch(self, idx: torch.Tensor, nvalid: int): ...
+    def set_eval_noise(self, snr_db: Optional[float]): ...
     def read_metrics(self) -> Metrics: ...
     def reset_metrics(self): ...
     def sync_bn_stats(self): ...
@@ -80,11 +82,15 @@ class TorchBackend(Backend):
 
     def __init__(self, model: nn.Module, model_type: str, X: torch.Tensor, labels: torch.Tensor,
                  X_eval: torch.Tensor, labels_eval: torch.Tensor, ctx: DistContext, batch: int, lr: float,
-                 weight_decay: float, loss_weights: Sequence[float] = (1.0, 1.0)):
+                 weight_decay: float, loss_weights: Sequence[float] = (1.0, 1.0), noise_snr=None, noise_seed: int = 0):
         self.model = model
         self.model_type = model_type
         self.ctx = ctx
         self.device = X.device
+        # SNR noise (data/noise.py, the definition the engine's gather kernel is tested against): the training
+        # range (lo, hi) with a draw number that advances once per step, and the evaluation level
+        self.noise_snr, self.noise_seed, self.noise_draw = parse_snr_range(noise_snr), int(noise_seed), 0
+        self.eval_snr_db = None
         self.X, self.labels, self.X_eval, self.labels_eval = X, labels, X_eval, labels_eval
         self.B = batch
         self.names, self.ncls = _report_tasks(model_type)
@@ -137,6 +143,9 @@ class TorchBackend(Backend):
     def train_batch(self, idx: torch.Tensor):
         self.model.train()
         x, lab = self.X[idx], self.labels[idx]
+        if self.noise_snr is not None:
+            x = self._noisy(x, idx, self.noise_seed, self.noise_draw, snr=self.noise_snr)
+            self.noise_draw += 1
         loss = self._forward_losses(x, lab, True)
         self.opt.zero_grad(set_to_none=False)
         loss.backward()
@@ -155,10 +164,23 @@ class TorchBackend(Backend):
     def set_eval_data(self, X: torch.Tensor, labels: torch.Tensor):
         self.X_eval, self.labels_eval = X, labels
 
+    def set_eval_noise(self, snr_db: Optional[float]):
+        """Evaluate the clean eval set at ``snr_db`` dB (evaluation stream, draw 0; None: clean)."""
+        self.eval_snr_db = None if snr_db is None else float(snr_db)
+
+    @staticmethod
+    def _noisy(x: torch.Tensor, idx: torch.Tensor, seed: int, draw: int, **level) -> torch.Tensor:
+        """``x`` = X[idx] with the noise of dataset rows ``idx`` (numpy fp64 on the host, rounded to fp32)."""
+        y = noisy_rows(x.detach().cpu().numpy(), idx.cpu().numpy(), seed, draw, **level)
+        return torch.from_numpy(y.astype(np.float32)).to(x.device)
+
     @torch.no_grad()
     def eval_batch(self, idx: torch.Tensor, nvalid: int):
         self.model.eval()
-        self._forward_losses(self.X_eval[idx], self.labels_eval[idx], False, nvalid)
+        x = self.X_eval[idx]
+        if self.eval_snr_db is not None:
+            x = self._noisy(x, idx, EVAL_SEED, 0, snr_db=self.eval_snr_db)
+        self._forward_losses(x, self.labels_eval[idx], False, nvalid)
 
     def read_metrics(self) -> Metrics:
         m = Metrics(self.names, self.ncls)
@@ -180,10 +202,11 @@ class TorchBackend(Backend):
             if s:
                 moments[names[id(p)]] = (s["exp_avg"].detach().cpu().clone(), s["exp_avg_sq"].detach().cpu().clone())
                 step = float(s["step"])
-        return {"adam_by_name": moments, "adam_step": step}
+        return {"adam_by_name": moments, "adam_step": step, "noise_draw": int(self.noise_draw)}
 
     def load_optimizer_state(self, st: dict):
         moments, step = portable_adam_state(st, self.model)
+        self.noise_draw = int(st.get("noise_draw", self.noise_draw))  # --resume continues the noise sequence
         for n, p in self.model.named_parameters():
             if n in moments:
                 m, v = moments[n]
@@ -197,7 +220,8 @@ class EngineBackend(Backend):
     def __init__(self, model: nn.Module, model_type: str, X: torch.Tensor, labels: torch.Tensor,
                  X_eval: torch.Tensor, labels_eval: torch.Tensor, ctx: DistContext, batch: int, lr: float,
                  weight_decay: float, loss_weights: Sequence[float] = (1.0, 1.0), use_graph: bool = True,
-                 tune: bool = False, seed: int = 0, sync_bn: bool = False):
+                 tune: bool = False, seed: int = 0, sync_bn: bool = False, noise_snr=None, noise_seed: int = 0,
+                 resident: bool = True):
         from .inception import InceptionProgram
         from .lowering import build_for_stream_buckets
         from .mtl import MTLProgram
@@ -257,8 +281,10 @@ class EngineBackend(Backend):
         lab_eval = labels_eval if labels_eval is not None else labels
         self.runner = StepRunner(self.prog, X, labels, use_graph=use_graph,
                                  allreduce=FlatGradAllReducer(ctx, capture=captured) if ctx.enabled else None,
-                                 X_eval=X_eval if X_eval is not None else X, labels_eval=lab_eval)
+                                 X_eval=X_eval if X_eval is not None else X, labels_eval=lab_eval, resident=resident)
         self.runner.set_lr(lr)
+        if noise_snr is not None:  # training augmentation: fresh SNR noise every step, added by the gather
+            self.runner.set_train_noise(parse_snr_range(noise_snr), noise_seed)
         self.B = batch
 
     def set_lr(self, lr: float):
@@ -277,6 +303,10 @@ class EngineBackend(Backend):
 
     def set_eval_data(self, X: torch.Tensor, labels: torch.Tensor):
         self.runner.set_eval_source(X, labels)
+
+    def set_eval_noise(self, snr_db: Optional[float]):
+        """Evaluate the clean eval set at ``snr_db`` dB (evaluation stream, draw 0; None: clean)."""
+        self.runner.set_eval_noise(snr_db, draw=0)
 
     def eval_batch(self, idx: torch.Tensor, nvalid: int):
         if idx.numel() < self.B:  # pad the last batch (BN uses running stats in eval: padding is inert)
@@ -319,6 +349,7 @@ class EngineBackend(Backend):
         st = {"adam_by_name": moments, "adam_step": float(f.step.item())}
         if hasattr(self.prog, "seed"):  # Model C's dropout RNG counter (stream + step)
             st["dropout_counter"] = int(self.prog.seed.item())
+        st["noise_draw"] = int(self.runner.noise_draw["train"].item())  # the training noise's draw number
         return st
 
     def load_optimizer_state(self, st: dict):
@@ -330,6 +361,8 @@ class EngineBackend(Backend):
                 f.exp_avg[o:o + p.numel()].copy_(moments[n][0].reshape(-1))
                 f.exp_avg_sq[o:o + p.numel()].copy_(moments[n][1].reshape(-1))
         f.step.fill_(step)
+        if "noise_draw" in st:  # --resume continues the noise sequence
+            self.runner.noise_draw["train"].fill_(int(st["noise_draw"]))
         if "dropout_counter" in st and hasattr(self.prog, "seed"):
             # keep this rank's stream (high word), continue the saved step count (low word)
             cur = int(self.prog.seed.item())

@@ -15,7 +15,9 @@ import torch
 
 
 def check_step(prog, X: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor, use_graph: bool = False,
-               runs: int = 2) -> Dict[str, object]:
+               runs: int = 2, noise: Optional[tuple] = None) -> Dict[str, object]:
+    """``noise``: ((lo, hi), seed) -- the step trains with SNR noise in its gather (StepRunner.set_train_noise), every
+    run at draw 0."""
     from .step import StepRunner
     f = prog.flat
     state = [f.params, f.exp_avg, f.exp_avg_sq, f.bn_mean, f.bn_var, f.bn_nbt, f.step] + \
@@ -26,6 +28,8 @@ def check_step(prog, X: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor, u
         for t, s in zip(state, saved):
             t.copy_(s)
         r = StepRunner(prog, X, labels, use_graph=use_graph, allreduce=lambda g: None)
+        if noise is not None:
+            r.set_train_noise(noise[0], noise[1], draw=0)
         r.pack_weights()
         r.train_step(idx)
         torch.cuda.synchronize()

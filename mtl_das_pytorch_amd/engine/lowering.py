@@ -8,13 +8,14 @@ from typing import Callable, Dict, List, Optional
 
 import torch
 
-from ..ops.functional import WGRAD_PATCH, WGRAD_TILES, wgrad_ktiles
+from ..ops.functional import WGRAD_PATCH, WGRAD_TILES, noise_args, wgrad_ktiles
 from ..ops.hip import lib
 from .core import (GRAD_DT, Act, BNLayer, ConvLayer, P, build_optseg_table, build_wgfin_table, optimizer_segments,
                    pad_to)
 from .program import (COMM_STREAM, SPILL_STREAM, Launch, Phase, k_adam, k_step_inc, k_allreduce, k_ext_record, k_conv, k_gather, k_gather_windows, k_tail_bwd, k_tail_fwd,
                       k_tail_fwd_batched, k_wgfin, k_wgrad,
                       k_wgrad_batched, k_window_probs)
+from .program import NoiseSpec, k_gather_noise, k_noise_advance
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID, SIGMUL, ADD_RELU, POOL_RELU = range(6)
 
@@ -394,12 +395,13 @@ class LoweredProgram:
         """Bind the dataset tensors the gather launch reads (X [N,C,H,W] fp32, labels [N,2], idx [B])."""
         self.src = (X, labels, idx)
 
-    def gather_phase(self, X, labels, idx, clear: bool = False, cursor=None) -> Phase:
+    def gather_phase(self, X, labels, idx, clear: bool = False, cursor=None, noise: Optional[NoiseSpec] = None) -> Phase:
         """The batch gather; ``clear``: the same launch also zeroes the arena's zeroed region (what
         ``arena.clear`` does at the start of a training step), unless the guard allocator keeps every zeroed
         view in its own banded buffer -- then ``arena.clear`` runs first.  ``cursor``: ``idx`` is a
         [nrows][B] batch-index schedule and the gather takes row ``cursor`` mod nrows (the optimizer's
-        step-counter kernel advances the cursor: set_step_cursor)."""
+        step-counter kernel advances the cursor: set_step_cursor).  ``noise``: the gather adds SNR noise
+        (csrc/augment.hip); a training spec's phase ends with the launch that advances the draw number."""
         if cursor is not None and (idx.dim() != 2 or idx.shape[1] != self.B):
             raise ValueError(f"index schedule must be [nrows][{self.B}], got {tuple(idx.shape)}")
         ph = Phase("gather")
@@ -411,6 +413,19 @@ class LoweredProgram:
             if zero is None:
                 ph.add("clear", lambda st: self.arena.clear())
                 zero = []
+        if noise is not None:
+            if tuple(noise.power.shape) != (X.shape[0], X.shape[1]):
+                raise ValueError("the noise power table does not belong to this dataset")
+            d = noise_args(noise.power, noise.snr, noise.draw, noise.seed, 0 if noise.train else 2)
+            d.update({"X": P(X), "idx": P(idx), "lab": P(labels), "lab_w": self.label_width, "out": P(self.x),
+                      "lab_out": P(self.labels), "B": self.B, "Cin": X.shape[1], "H": self.H0, "W": self.W0,
+                      "taps": self.stem_pack[0], "off": self.stem_pack[1], "zero": zero, "cursor": P(cursor),
+                      "nrows": idx.shape[0] if cursor is not None else 0})
+            ph.add("gather_noise", k_gather_noise, d)
+            if noise.train:
+                ph.add("noise_advance", k_noise_advance, noise.draw)
+            ph.keep = (X, labels, idx, cursor, noise.power, noise.snr, noise.draw)
+            return ph
         ph.add("gather", k_gather, X, idx, labels, self.label_width, self.x, self.labels, self.B, X.shape[1], self.H0,
                self.W0, *self.stem_pack, zero, cursor)
         return ph

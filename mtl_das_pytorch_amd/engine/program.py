@@ -396,6 +396,27 @@ def k_gather(X, idx, lab, lab_w, out, lab_out, B, Cin, H, W, taps, off, zero, cu
                        idx.shape[0] if cursor is not None else 0)
 
 
+class NoiseSpec:
+    """The SNR noise of a gather phase (LoweredProgram.gather_phase ``noise``): the bound set's power table [N, C], the
+    device fp32 (lo, hi) level pair and int64 draw number -- device values, so changing them re-captures nothing --
+    and the launch constants: the 64-bit seed and whether the phase trains (Gaussian stream 0 and a draw advance
+    after the gather) or evaluates (stream 2, the draw stays)."""
+    __slots__ = ("power", "snr", "draw", "seed", "train")
+
+    def __init__(self, power, snr, draw, seed: int, train: bool):
+        self.power, self.snr, self.draw, self.seed, self.train = power, snr, draw, int(seed), bool(train)
+
+
+def k_gather_noise(d, st):
+    """The batch gather with SNR noise (csrc/augment.hip; ``d``: the gather's arguments and the noise inputs)."""
+    lib().gather_batch_noise(st, d)
+
+
+def k_noise_advance(draw, st):
+    """``draw += 1`` by one thread, after the noise gather of a training step (its blocks all read the draw)."""
+    lib().noise_advance(draw.data_ptr(), st)
+
+
 def k_gather_windows(d, st):
     """The batch's windows cut from a resident recording (csrc/window.hip; ``d``: the launch's argument dict)."""
     lib().gather_windows(st, d)

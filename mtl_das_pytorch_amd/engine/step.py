@@ -19,6 +19,10 @@ The batch indices come from a device-resident schedule (set_index_schedule: the 
 the optimizer kernel advances the cursor) or from a persistent device buffer the host refreshes before each
 replay; the learning rate is a device scalar, so the reference's LR schedule never forces a re-capture.
 
+With SNR noise on (set_train_noise / set_eval_noise) the gather is the noise gather of csrc/augment.hip: the levels
+and the draw number are device scalars too, a training gather phase ends with the launch that advances the draw, and
+the power table of a bound set is computed once.
+
 An inference step over a resident recording (set_window_source / infer_step) is
 
     [window gather from the recording] [eval forward] [probabilities -> resident table, batch cursor++]
@@ -32,7 +36,8 @@ from typing import Callable, Dict, List, Optional
 
 import torch
 
-from .program import EngineStreams, EventKeeper, ExtEvent, Phase
+from ..data.noise import EVAL_SEED, parse_snr_range
+from .program import EngineStreams, EventKeeper, ExtEvent, NoiseSpec, Phase
 
 
 class StateSnapshot:
@@ -66,8 +71,11 @@ class StepRunner:
 
     def __init__(self, program, X: torch.Tensor, labels: torch.Tensor, use_graph: bool = True,
                  allreduce: Optional[Callable[[torch.Tensor], None]] = None, X_eval: torch.Tensor = None,
-                 labels_eval: torch.Tensor = None):
+                 labels_eval: torch.Tensor = None, resident: bool = True):
         self.p = program
+        # False: the sources are a streaming ring whose rows change under the step (data/stream.py), not a
+        # resident set -- the SNR noise, keyed by dataset row and scaled by a per-row power table, cannot serve it
+        self.resident = resident
         self.use_graph = use_graph and program.device.type == "cuda"
         self.allreduce = allreduce
         B = program.B
@@ -101,6 +109,12 @@ class StepRunner:
         self.window = None  # resident-recording inference (set_window_source): (rec, fs, ts, probs, lo, hi)
         self.window_cursor = None
         self.window_key = None  # what the source's owner knows it by (inference.resident_probs: shape and starts)
+        # SNR noise in the gather (set_train_noise / set_eval_noise): per mode the launch constant (seed; None: off)
+        # and the device scalars the captured graphs read -- fp32 (lo, hi) and the int64 draw number
+        self.noise_seed = {"train": None, "eval": None}
+        self.noise_snr = {k: torch.zeros(2, dtype=torch.float32, device=program.device) for k in ("train", "eval")}
+        self.noise_draw = {k: torch.zeros(1, dtype=torch.int64, device=program.device) for k in ("train", "eval")}
+        self._power = {}  # mode -> (X, its power table): cached by tensor identity
 
     def set_index_schedule(self, schedule: Optional[torch.Tensor]):
         """Train from a device-resident [nrows][B] batch-index schedule: ``train_step()`` without indices then
@@ -128,6 +142,57 @@ class StepRunner:
         self.cursor.zero_()
 
     # -------------------------------------------------------------------------------------------
+    def _set_noise(self, mode: str, snr, seed: int, draw: Optional[int]):
+        kinds = [k for k in self.graphs if k.startswith("train")] if mode == "train" else ["eval"]
+        new_seed = None if snr is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        if snr is not None and not self.resident:
+            raise ValueError("SNR noise needs a resident dataset: the streaming ring's rows (--dataset_ram False) "
+                             "are not dataset rows")
+        if new_seed != self.noise_seed[mode]:  # on, off or another seed (a launch constant): other launches
+            for kind in kinds:
+                self._drop_graph(kind)
+            self.noise_seed[mode] = new_seed
+        if snr is None:
+            self._power.pop(mode, None)
+            return
+        lo, hi = parse_snr_range(snr)
+        self.noise_snr[mode].copy_(torch.tensor([lo, hi], dtype=torch.float32))
+        if draw is not None:
+            self.noise_draw[mode].fill_(int(draw))
+        self._noise_power(mode)
+
+    def set_train_noise(self, snr, seed: int = 0, draw: Optional[int] = None):
+        """Train on noisy inputs, fresh noise every step (csrc/augment.hip, data/noise.py): ``snr`` = (lo, hi) in dB
+        -- every sample of every step draws its level uniformly from the range -- or None for the clean gather.
+        The step's gather phase advances the draw number, so step k of a run sees draw d0 + k.  Turning the noise
+        on or off (or another seed) drops the captured training graphs; another range only writes the device
+        scalars they read.  ``draw``: restart the draw number (None keeps it)."""
+        self._set_noise("train", snr, seed, draw)
+
+    def set_eval_noise(self, snr_db: Optional[float], draw: int = 0, seed: int = EVAL_SEED):
+        """Evaluate the (clean) eval source at a fixed SNR: the eval step's gather adds the evaluation noise of
+        ``draw`` at ``snr_db`` dB, the same for every model and run; None returns to the clean gather.  Turning it
+        on or off drops the captured eval graph; another level or draw only writes device scalars."""
+        self._set_noise("eval", snr_db, seed, draw)
+
+    def _noise_power(self, mode: str) -> torch.Tensor:
+        """The power table of the mode's bound source, computed once per set (cached by tensor identity)."""
+        from ..ops.functional import sample_power
+        X = self.sources[mode if mode in self.sources else "train"][0]
+        cur = next((c for c in self._power.values() if c[0] is X), None)  # (both modes may read one set)
+        if cur is None:
+            cur = (X, sample_power(X))
+        self._power[mode] = cur
+        return cur[1]
+
+    def _noise_spec(self, mode: str) -> Optional[NoiseSpec]:
+        if self.noise_seed[mode] is None:
+            return None
+        if not self.resident:
+            raise ValueError("SNR noise needs a resident dataset")
+        return NoiseSpec(self._noise_power(mode), self.noise_snr[mode], self.noise_draw[mode], self.noise_seed[mode],
+                         train=mode == "train")
+
     def _mutable_state(self, kind: Optional[str] = None) -> List[torch.Tensor]:
         f = self.p.flat
         # the inference step advances its batch cursor and fills rows of the probability table: a warm-up that
@@ -135,7 +200,9 @@ class StepRunner:
         infer = [self.window_cursor, self.window[3]] if kind == "infer" else []
         return ([f.params, f.grads, f.exp_avg, f.exp_avg_sq, f.bn_mean, f.bn_var, f.bn_nbt, f.step, self.p.metrics,
                  self.p.confusion, self.p.logp] + list(self.p.extra_state)
-                + ([self.cursor] if self.cursor is not None else []) + infer)
+                + ([self.cursor] if self.cursor is not None else []) + infer
+                # the training gather phase advances the draw number: the first real step uses the draw that was set
+                + ([self.noise_draw["train"]] if self.noise_seed["train"] is not None else []))
 
     def pack_weights(self):
         """(Re)build the bf16 MFMA weight images from the fp32 masters (after init / load_state_dict)."""
@@ -153,7 +220,8 @@ class StepRunner:
         # a training step's gather also zeroes the arena's accumulators (one launch; arena.clear otherwise)
         sched = self.schedule is not None and kind.startswith("train")
         gather = p.gather_phase(X, lab, self.schedule if sched else self.idx, clear=kind.startswith("train"),
-                                cursor=self.cursor if sched else None)
+                                cursor=self.cursor if sched else None,
+                                noise=self._noise_spec("train" if kind.startswith("train") else "eval"))
         if kind == "train_ext":
             if self._bwd_ext is None:
                 self.ext_events = [ExtEvent() for _ in self.buckets]
@@ -264,6 +332,8 @@ class StepRunner:
             return
         self.sources["eval"] = (X, labels)
         self._drop_graph("eval")
+        if self.noise_seed["eval"] is not None:
+            self._noise_power("eval")
 
     def eval_step(self, idx: torch.Tensor):
         if not self._packed:

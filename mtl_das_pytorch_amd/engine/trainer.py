@@ -80,17 +80,18 @@ class ResidentSource:
         pass
 
 
-def load_datasets(cfg: TrainConfig, device):
+def load_datasets(cfg: TrainConfig, device, synthetic_noise: bool = True):
     """``(train, val)`` data sources (``ResidentSource`` or, with ``--dataset_ram False``, a
     ``DiskBatchStream``); labels are ``[N,2]`` (distance, event) or joint ``[N]``.  Test mode returns
-    ``(None, test_set)``."""
+    ``(None, test_set)``.  ``synthetic_noise`` False: the synthetic samples' clean signals (same draws otherwise)."""
     joint = cfg.model == "multi_classifier"
     if cfg.synthetic > 0:
         per = cfg.synthetic
         d = torch.arange(N_DIST).repeat_interleave(2 * per)
         e = torch.arange(2).repeat_interleave(per).repeat(N_DIST)
         seed = cfg.synthetic_seed + (7919 if cfg.is_test else 0)
-        X, d_, e_ = generate(len(d), seed=seed, device="cpu", in_channels=cfg.in_channels, distance=d, event=e)
+        X, d_, e_ = generate(len(d), seed=seed, device="cpu", in_channels=cfg.in_channels, distance=d, event=e,
+                             noise=synthetic_noise)
         lab = (d_ + N_DIST * e_) if joint else torch.stack([d_, e_], 1)
         if cfg.is_test:
             return None, ResidentSource(X.to(device), lab.to(device))
@@ -173,12 +174,17 @@ class Trainer:
         if self.train_src is None:  # test mode evaluates the (whole) test set
             self.train_src = self.val_src
         X, Y, Xv, Yv = self.train_src.X, self.train_src.labels, self.val_src.X, self.val_src.labels
+        resident = isinstance(self.train_src, ResidentSource) and isinstance(self.val_src, ResidentSource)
+        noise = None if cfg.is_test else cfg.noise_snr_db  # training augmentation (data/noise.py)
+        if (noise is not None or cfg.snr_sweep) and not resident:
+            raise ValueError("--noise_snr_db / --snr_sweep need a resident dataset (--dataset_ram True)")
         kw = dict(ctx=self.ctx, batch=cfg.batch_size, lr=cfg.lr, weight_decay=cfg.weight_decay,
-                  loss_weights=cfg.loss_weights)
+                  loss_weights=cfg.loss_weights, noise_snr=noise,
+                  noise_seed=cfg.seed if cfg.noise_seed is None else cfg.noise_seed)
         if self.backend_name == "engine":
             self.model.to(self.device)
             self.backend = EngineBackend(self.model, cfg.model, X, Y, Xv, Yv, use_graph=cfg.graph, tune=cfg.tune,
-                                         seed=cfg.seed, sync_bn=cfg.sync_bn, **kw)
+                                         seed=cfg.seed, sync_bn=cfg.sync_bn, resident=resident, **kw)
         else:
             if cfg.sync_bn and self.ctx.enabled:
                 self.model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(self.model)
@@ -209,6 +215,8 @@ class Trainer:
                 self.validate(epoch)
                 self._save_resume(epoch, val_done=True)
                 if cfg.is_test:
+                    if cfg.snr_sweep:
+                        self.snr_sweep(cfg.snr_sweep)
                     break
             if epoch < E:
                 self.train_epoch(epoch, sampler)
@@ -337,23 +345,54 @@ class Trainer:
         return m, batch_means
 
     @torch.no_grad()
-    def evaluate(self, X: torch.Tensor, labels: torch.Tensor) -> dict:
+    def evaluate(self, X: torch.Tensor, labels: torch.Tensor, snr_db: Optional[float] = None) -> dict:
         """Accuracy / MAE / loss of the current model on an arbitrary resident set (e.g. a held-out test
-        set, or one at a given SNR) without touching curves, checkpoints or the LR schedule."""
+        set, or one at a given SNR) without touching curves, checkpoints or the LR schedule.  ``snr_db``: the
+        clean set ``X`` is scored at that SNR -- the evaluation noise of data/noise.py (stream 2, draw 0, a fixed
+        seed: the same test noise for every model and run), added on the device by the engine's gather."""
+        return self.evaluate_levels(X, labels, [snr_db])[0]
+
+    @torch.no_grad()
+    def evaluate_levels(self, X: torch.Tensor, labels: torch.Tensor, levels) -> List[dict]:
+        """:meth:`evaluate` of one resident set at several SNR levels (None: clean), bound once: between two levels
+        the engine only writes the device scalars its captured eval graph reads."""
         self.backend.sync_bn_stats()
         self.backend.set_eval_data(X, labels)
+        outs, n = [], len(X)
         try:
-            m, batch_means = self._eval_pass(ResidentSource(X, labels))
+            for snr_db in levels:
+                self.backend.set_eval_noise(snr_db)
+                m, batch_means = self._eval_pass(ResidentSource(X, labels))
+                out = {"acc": {m.names[t]: m.acc(t) for t in range(len(m.names))},
+                       "loss": {m.names[t]: float(batch_means[t] / n) for t in range(len(m.names))}}
+                if "distance" in m.names:
+                    cm = m.cm[m.names.index("distance")]
+                    out["mae_m"] = mae_from_confusion(cm)
+                    out["distance_cm"] = cm.tolist()
+                outs.append(out)
         finally:
+            self.backend.set_eval_noise(None)
             self.backend.set_eval_data(self.val_src.X, self.val_src.labels)
-        n = len(X)
-        out = {"acc": {m.names[t]: m.acc(t) for t in range(len(m.names))},
-               "loss": {m.names[t]: float(batch_means[t] / n) for t in range(len(m.names))}}
-        if "distance" in m.names:
-            cm = m.cm[m.names.index("distance")]
-            out["mae_m"] = mae_from_confusion(cm)
-            out["distance_cm"] = cm.tolist()
-        return out
+        return outs
+
+    def snr_sweep(self, levels) -> List[dict]:
+        """Score the resident clean test set at each SNR level from one upload: one console line per level
+        (event acc / distance acc / MAE) and ``snr_sweep.json`` in the run directory (rank 0)."""
+        import json
+        src = self.val_src
+        if self.cfg.synthetic > 0:  # the synthetic test samples carry their own 6-20 dB noise: sweep their clean signals
+            src = load_datasets(self.cfg, self.device, synthetic_noise=False)[1]
+        rows = []
+        for snr, r in zip(levels, self.evaluate_levels(src.X, src.labels, list(levels))):
+            row = {"snr_db": float(snr), "acc": r["acc"], "loss": r["loss"], "mae_m": r.get("mae_m")}
+            rows.append(row)
+            mae = "n/a" if row["mae_m"] is None else "{:.4f}".format(row["mae_m"])
+            self.print("SNR {:g} dB: event acc {}  distance acc {}  MAE (m) {}".format(
+                snr, *("{:.5f}".format(r["acc"][t]) if t in r["acc"] else "n/a" for t in ("event", "distance")), mae))
+        if self.is_main:
+            with open(os.path.join(self.save_dir, "snr_sweep.json"), "w") as f:
+                json.dump({"model": self.cfg.model, "samples": self.n_val, "levels": rows}, f, indent=1)
+        return rows
 
     @torch.no_grad()
     def validate(self, epoch: int):

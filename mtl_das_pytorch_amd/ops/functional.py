@@ -629,6 +629,79 @@ def gather_batch(X: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor):
     return out, lab
 
 
+def sample_power(X: torch.Tensor) -> torch.Tensor:
+    """Mean power of every clean plane of a resident set: X [N, C, H, W] fp32 -> P [N, C] fp32, the mean over the
+    plane of (x - mean(x))^2 (data/noise.py; two passes with fp64 accumulators)."""
+    _check(X, torch.float32)
+    if X.dim() != 4:
+        raise ValueError("dataset must be [N, C, H, W]")
+    N, C, H, W = X.shape
+    P = torch.empty(N, C, device=X.device, dtype=torch.float32)
+    lib().sample_power(ptr(X), ptr(P), N * C, H * W, stream())
+    return P
+
+
+def noise_args(power: torch.Tensor, snr: torch.Tensor, draw: torch.Tensor, seed: int, noise_stream: int) -> dict:
+    """The noise inputs of :func:`gather_batch_noise` as the binding reads them: the device power table [N, C], the
+    device (lo, hi) fp32 pair, the device int64 draw number, and the launch constants (seed, stream id)."""
+    _check(power, torch.float32)
+    _check(snr, torch.float32)
+    _check(draw, torch.int64)
+    if snr.numel() != 2 or draw.numel() != 1:
+        raise ValueError("snr must hold (lo, hi) and draw one number")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return {"power": ptr(power), "snr": ptr(snr), "draw": ptr(draw), "seed_lo": seed & 0xFFFFFFFF,
+            "seed_hi": seed >> 32, "noise_stream": int(noise_stream)}
+
+
+def gather_batch_noise(X: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor, power: torch.Tensor,
+                       snr: torch.Tensor, draw: torch.Tensor, seed: int, noise_stream: int = 0, taps: int = 0,
+                       off: int = 0, zero: Sequence[torch.Tensor] = (), cursor: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None, dbg: Optional[torch.Tensor] = None):
+    """:func:`gather_batch` with SNR noise (data/noise.py): every real element is ``bf16(x + sigma * g)``, padding
+    channels and out-of-image taps stay 0.  ``power``: :func:`sample_power` of ``X``; ``snr``: device fp32 (lo, hi);
+    ``draw``: device int64 scalar; ``noise_stream``: 0 training, 2 evaluation.  ``idx``: int64 [B], or with
+    ``cursor`` (a device int64 scalar) a [nrows, B] schedule whose row ``cursor`` mod nrows is gathered.  ``taps`` /
+    ``off``: the 1-channel stem's vertical tap packing.  ``zero``: up to 4 tensors the launch clears (16-byte aligned
+    and sized).  ``out``: the [B, H, W, 8] bf16 output to write; ``dbg``: an fp32 [B, Cin, H, W] tensor that
+    receives the unrounded noisy values (test hook).  Returns (out, labels)."""
+    _check(X, torch.float32)
+    _check(idx, torch.int64)
+    _check(labels, torch.int64)
+    N, Cin, H, W = X.shape
+    if tuple(power.shape) != (N, Cin):
+        raise ValueError(f"power table must be [{N}, {Cin}]")
+    B = idx.shape[-1] if cursor is not None else idx.numel()
+    if cursor is not None:
+        _check(cursor, torch.int64)
+        if idx.dim() != 2:
+            raise ValueError("a cursor needs a [nrows, B] index schedule")
+    lw = labels.shape[1] if labels.dim() == 2 else 1
+    if out is None:
+        out = torch.empty(B, H, W, 8, device=X.device, dtype=torch.bfloat16)
+    _check(out, torch.bfloat16)
+    if out.numel() < B * H * W * 8:
+        raise ValueError("output too small")
+    if dbg is not None:
+        _check(dbg, torch.float32)
+        if dbg.numel() < B * Cin * H * W:
+            raise ValueError("dbg too small")
+    lab = torch.empty(B, lw, device=X.device, dtype=torch.int64)
+    d = noise_args(power, snr, draw, seed, noise_stream)
+    d.update({"X": ptr(X), "idx": ptr(idx), "lab": ptr(labels), "lab_w": lw, "out": ptr(out), "lab_out": ptr(lab),
+              "B": B, "Cin": Cin, "H": H, "W": W, "taps": taps, "off": off,
+              "zero": [(z.data_ptr(), z.numel() * z.element_size()) for z in zero],
+              "cursor": ptr(cursor), "nrows": idx.shape[0] if cursor is not None else 0, "dbg": ptr(dbg)})
+    lib().gather_batch_noise(stream(), d)
+    return out, lab
+
+
+def noise_advance(draw: torch.Tensor):
+    """``draw += 1`` on the device (the launch a training gather phase appends after its noise gather)."""
+    _check(draw, torch.int64)
+    lib().noise_advance(ptr(draw), stream())
+
+
 def _starts(s, device) -> torch.Tensor:
     """A window-start table as the kernels read it: int32 on the device."""
     return torch.as_tensor(s).to(device=device, dtype=torch.int32).contiguous()

@@ -55,6 +55,9 @@ class TrainConfig:
     synthetic: int = 0                    # >0: N synthetic samples per (distance, event) class, no dataset needed
     synthetic_seed: int = 0
     snr_db: Optional[float] = None        # optional SNR noise injection (reference add_gaussian, disabled there)
+    noise_snr_db: Optional[List[float]] = None  # [lo, hi] dB: on-device training noise, fresh every step (data/noise.py)
+    noise_seed: Optional[int] = None      # seed of the training noise (default: --seed)
+    snr_sweep: List[float] = field(default_factory=list)  # test mode: levels (dB) the clean test set is scored at
     seed: int = 0
     graph: bool = True
     tune: bool = False
@@ -114,6 +117,13 @@ def build_parser(is_test: bool) -> argparse.ArgumentParser:
     g.add_argument("--synthetic", type=int, default=0, help="synthetic samples per (distance, event) class")
     g.add_argument("--synthetic_seed", type=int, default=0)
     g.add_argument("--snr_db", type=float, default=None)
+    g.add_argument("--noise_snr_db", type=str, default=None, metavar="LO[,HI]",
+                   help="train on noisy inputs: every sample of every step gets fresh Gaussian noise at an SNR drawn "
+                        "uniformly from [LO, HI] dB (one value: LO = HI), added on the device by the batch gather; "
+                        "needs --dataset_ram True")
+    g.add_argument("--noise_seed", type=int, default=None, help="seed of the training noise (default: --seed)")
+    g.add_argument("--snr_sweep", type=str, default=None, metavar="L1,L2,...",
+                   help="test mode: after the test pass, score the same clean test set at each SNR level (dB)")
     g.add_argument("--seed", type=int, default=0)
     g.add_argument("--graph", type=str2bool, default=True, help="capture each step into a HIP graph")
     g.add_argument("--tune", type=str2bool, default=False, help="autotune kernel configs at start-up")
@@ -148,6 +158,15 @@ def config_from_args(args: argparse.Namespace, is_test: bool) -> TrainConfig:
         d["backend"] = "torch"
     if d.get("debug"):
         d["graph"] = False
+    from ..data.noise import parse_snr_range
+    rng = parse_snr_range(d.get("noise_snr_db"))
+    d["noise_snr_db"] = None if rng is None else list(rng)
+    if d.get("noise_seed") is None:
+        d["noise_seed"] = d.get("seed", 0)
+    d["snr_sweep"] = [float(t) for t in str(d.get("snr_sweep") or "").split(",") if t.strip() != ""]
+    if d["noise_snr_db"] is not None and not d.get("dataset_ram", True):
+        raise ValueError("--noise_snr_db needs a resident dataset (--dataset_ram True): noise on the disk-streaming "
+                         "ring is not supported")
     return TrainConfig(**d)
 
 
