@@ -438,8 +438,45 @@ void pool3(int is_max, int backward, int64_t stream, py::dict d) {
   a.B = (int)I(d, "B"); a.H = (int)I(d, "H"); a.W = (int)I(d, "W"); a.C = (int)I(d, "C");
   a.Ho = (int)I(d, "Ho"); a.Wo = (int)I(d, "Wo");
   a.am = P<uint8_t>(d, "am");
-  if (a.C % 8) throw std::runtime_error("pool3: C % 8");
-  if (a.am && !is_max) throw std::runtime_error("pool3: argmax only for max pooling");
+  // everything the kernels assume is refused here: they check no bounds of their own
+  auto bad = [](const std::string& what) { throw std::runtime_error("pool3: " + what); };
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  if (a.B <= 0 || a.H <= 0 || a.W <= 0 || a.C <= 0) bad("B, H, W, C must be positive");
+  if (a.C % 8) bad("C % 8");
+  if (a.am && !is_max) bad("am: argmax only for max pooling");
+  if (is_max) {
+    if (a.H < 3 || a.W < 3) bad("H, W: a max pool needs a 3 x 3 map");
+    if (a.Ho != (a.H - 3) / 2 + 1 || a.Wo != (a.W - 3) / 2 + 1) bad("Ho, Wo must be ((H - 3) / 2 + 1, (W - 3) / 2 + 1)");
+  } else if (a.Ho != a.H || a.Wo != a.W) {
+    bad("Ho, Wo must be (H, W) for the average pool");
+  }
+  auto pitch = [&](const char* name, int ld) {
+    if (ld % 8 || ld < a.C) bad(std::string(name) + " must be a multiple of 8 and >= C");
+  };
+  if (reinterpret_cast<uintptr_t>(a.am) & 7) bad("am must be 8-byte aligned");
+  if (!backward) {
+    if (!a.x) bad("x is null");
+    if (!a.y) bad("y is null");
+    if (!al16(a.x)) bad("x must be 16-byte aligned");
+    if (!al16(a.y)) bad("y must be 16-byte aligned");
+    pitch("ldx", a.ldx);
+    pitch("ldy", a.ldy);
+  } else {
+    if (!a.dx) bad("dx is null");
+    if (!al16(a.dx)) bad("dx must be 16-byte aligned");
+    pitch("lddx", a.lddx);
+    if (a.g.n < 1) bad("g: no gradient source");
+    for (int i = 0; i < a.g.n; ++i) {
+      if (!a.g.p[i]) bad("g: null gradient source");
+      if (!al16(a.g.p[i])) bad("g must be 16-byte aligned");
+      pitch(a.g.n == 1 ? "ldg" : "a source pitch (ldg)", a.g.ld[i]);
+    }
+    if (is_max && !a.am) {  // the windows are re-read
+      if (!a.x) bad("x is null (max pool backward without am)");
+      if (!al16(a.x)) bad("x must be 16-byte aligned");
+      pitch("ldx", a.ldx);
+    }
+  }
   check(launch_pool3(is_max, backward, a, S(stream)), "pool3");
 }
 
@@ -450,10 +487,6 @@ void synth_das(int64_t stream, py::dict d) {
   a.noise = (int)I(d, "noise", 1);
   a.key = (uint64_t)I(d, "key"); a.sample0 = I(d, "sample0", 0);
   check(launch_synth_das(a, (int)I(d, "n"), S(stream)), "synth_das");
-}
-
-void grad_sum(py::list g, int64_t out, int ldo, int64_t M, int C, int64_t stream) {
-  check(launch_grad_sum(parse_grads(g), reinterpret_cast<bf16_t*>(out), ldo, M, C, S(stream)), "grad_sum");
 }
 
 void adam_pack(int64_t stream, py::dict d) {
@@ -527,7 +560,6 @@ PYBIND11_MODULE(_mda_hip, m) {
   m.def("wgrad_table", &wgrad_table);
   m.def("wgrad_batched", &wgrad_batched, py::arg("cfg"), py::arg("table"), py::arg("nj"), py::arg("nblocks"),
         py::arg("stream"), py::arg("cap") = 0);
-  m.def("grad_sum", &grad_sum);
   m.def("synth_das", &synth_das);
   m.def("philox_kat", [](int64_t ctr, uint64_t key, int64_t out, int n, int64_t stream) {
     check(launch_philox_kat(reinterpret_cast<const uint32_t*>(static_cast<intptr_t>(ctr)), key,

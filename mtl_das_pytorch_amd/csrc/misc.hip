@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void pool3_bwd_kernel(PoolArgs a) {
           float mx[8];
           int am[8];
 #pragma unroll
-          for (int j = 0; j < 8; ++j) { mx[j] = -INFINITY; am[j] = -1; }
+          for (int j = 0; j < 8; ++j) { mx[j] = -INFINITY; am[j] = 0; }  // (a window of -inf: position 0, as the forward)
           for (int kh = 0; kh < 3; ++kh)
             for (int kw = 0; kw < 3; ++kw) {
               float v[8];
@@ -259,25 +259,6 @@ __global__ void tick_kernel(uint64_t* buf, uint64_t* q, int i) {
 
 int launch_tick(uint64_t* buf, uint64_t* q, int i, hipStream_t st) {
   hipLaunchKernelGGL(tick_kernel, dim3(1), dim3(1), 0, st, buf, q, i);
-  return (int)hipGetLastError();
-}
-
-// sum of up to 6 bf16 gradient sources into one buffer (used where a consumer is not a fused tail)
-__global__ __launch_bounds__(256) void grad_sum_kernel(GradSrcs g, bf16_t* out, int ldo, int64_t M, int C) {
-  const int CG = C >> 3;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < M * CG; i += (int64_t)gridDim.x * 256) {
-    const int64_t p = i / CG;
-    const int c = (int)(i - p * CG) * 8;
-    float v[8];
-    gsum8(g, 0, p, c, v);
-    store8(out + p * ldo + c, v);
-  }
-}
-
-int launch_grad_sum(const GradSrcs& g, bf16_t* out, int ldo, int64_t M, int C, hipStream_t st) {
-  const int64_t n = M * (C / 8);
-  const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
-  hipLaunchKernelGGL(grad_sum_kernel, dim3(blocks), dim3(256), 0, st, g, out, ldo, M, C);
   return (int)hipGetLastError();
 }
 
