@@ -113,21 +113,14 @@ DEV void unpack8(uint4 u, float* v) {  // 8 bf16 -> fp32
     v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
   }
 }
-DEV void load8(const bf16_t* p, float* v) {
-  uint4 u = *reinterpret_cast<const uint4*>(p);
-  uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(w[i] << 16);
-    v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-  }
-}
-DEV void store8(bf16_t* p, const float* v) {
+DEV uint4 pack8(const float* v) {  // fp32 -> 8 bf16, each rounded to nearest even
   uint32_t w[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) w[i] = (uint32_t)f2bf(v[2 * i]) | ((uint32_t)f2bf(v[2 * i + 1]) << 16);
-  *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+  return make_uint4(w[0], w[1], w[2], w[3]);
 }
+DEV void load8(const bf16_t* p, float* v) { unpack8(*reinterpret_cast<const uint4*>(p), v); }
+DEV void store8(bf16_t* p, const float* v) { *reinterpret_cast<uint4*>(p) = pack8(v); }
 DEV void load8f(const float* p, float* v) {
   float4 a = *reinterpret_cast<const float4*>(p);
   float4 b = *reinterpret_cast<const float4*>(p + 4);
@@ -209,11 +202,11 @@ DEV void store4(bf16_t* p, const float* v) {
   w.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
   *reinterpret_cast<uint2*>(p) = w;
 }
-DEV void load4(const bf16_t* p, float* v) {
-  const uint2 u = *reinterpret_cast<const uint2*>(p);
+DEV void unpack4(uint2 u, float* v) {
   v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u);
   v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
 }
+DEV void load4(const bf16_t* p, float* v) { unpack4(*reinterpret_cast<const uint2*>(p), v); }
 
 // Per-BN-layer state. Everything is indexed by group z with the given strides (0 = shared).
 struct BNArgs {

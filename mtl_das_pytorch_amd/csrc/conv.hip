@@ -23,11 +23,13 @@
 //
 // The K dimension is walked in steps of 32 = four 8-channel groups; a per-block LDS table maps each
 // k-group to (segment, kh, kw, channel) so two-segment inputs (cat[F_shared, B_task]) need no concat.
-#include "kernels.h"
+//
+// The pieces conv_igemm shares with the LDS-staged kernels of conv_lds.hip / conv_patch.hip (BN-backward
+// constants, dz statistics, statistics flush) and the 8-wide normalise-on-load transform of the weight-gradient
+// staging are in conv_tile.h.
+#include "conv_tile.h"
 
 namespace mda {
-
-
 
 DEV int encode_kg(int i, int Ktot, int Cs8, int KW, int C0) {
   if (i * 8 >= Ktot) return 0;
@@ -37,11 +39,6 @@ DEV int encode_kg(int i, int Ktot, int Cs8, int KW, int C0) {
   if (seg) c -= C0;
   return c | (kw << 14) | (kh << 21) | (seg << 28) | (1 << 29);
 }
-
-template <int MODE>
-constexpr bool is_fwd() { return MODE == MODE_FWD || MODE == MODE_FWD_NOL; }
-template <int MODE>
-constexpr bool has_bns() { return MODE == MODE_DGRAD_BNS; }
 
 // Normalise-on-load: the 8 channels [c, c+8) of an im2col fragment are pre-BN conv outputs y; the operand
 // is act(y * scale + shift) (act = ReLU or identity), rounded to bf16 exactly as the BN tail that used to
@@ -147,21 +144,9 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
   for (int i = threadIdx.x; i < nkg; i += 256) s_tab[i] = encode_kg(i, Ktot, a.Cs >> 3, a.KW, a.src.C0);
   // MODE_DGRAD_BNS: dgrad + fused BN-backward statistics -- its own instantiation, so the extra registers
   // never lower the occupancy of the plain dgrads (104 -> 142 VGPRs measured when they shared one)
-  constexpr bool want_bnb = has_bns<MODE>();
-  const int bN = a.bN > 0 ? a.bN : a.N;  // the tail's channels (a concat gradient has more)
-  const int zb = a.bpgs == 0 ? 0 : z;    // one tail shared by every group: its constants are group 0's
-  if (want_bnb) {
-    for (int i = threadIdx.x; i < BN_T; i += 256) {
-      const int n = blk.y * BN_T + i;
-      float k[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (n < bN) {
-        bn_channel_bwd(a.bbn, zb, n, k[0], k[1], k[2], k[3]);
-        if (a.br_bn) bn_channel_bwd(a.bbn2, zb, n, k[4], k[5], k[6], k[7]);
-      }
-#pragma unroll
-      for (int q = 0; q < 8; ++q) s_bn[q * BN_T + i] = k[q];
-    }
-  }
+  constexpr bool want_bnb = MODE == MODE_DGRAD_BNS;
+  const int bN = bns_channels(a);
+  if (want_bnb) BNS_CONSTANTS(BN_T, z, blk.y * BN_T, s_bn);
   // MODE_FWD_NOL: the input is the previous conv's pre-BN y; its BN constants for all Cs channels go to
   // LDS, and block (0, 0) of each group performs that BN's running-statistics update and publishes its
   // batch constants for the backward (the work of the forward tail this mode replaces)
@@ -195,16 +180,10 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
     if (is_fwd<MODE>()) { py[f] = oh * a.sh - a.ph; px[f] = ow * a.sw - a.pw; }
     else { py[f] = oh + a.ph; px[f] = ow + a.pw; }
   }
-  const bf16_t* base0 = a.src.p[0] + a.src.gs[0] * z;
-  const bf16_t* base1 = a.src.p[1] ? a.src.p[1] + a.src.gs[1] * z : base0;
-  const int ld0 = a.src.ld[0], ld1 = a.src.ld[1];
-  const bf16_t* wz = a.w + a.wgs * z;
+  const ConvBases sb = conv_bases(a, z);
 
   f32x4 acc[FN][FM];
-#pragma unroll
-  for (int i = 0; i < FN; ++i)
-#pragma unroll
-    for (int f = 0; f < FM; ++f) acc[i][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+  acc_zero(acc);
 
   const int nks = a.Kpad >> 5;
   const int kchunk = (nks + KSPLIT - 1) / KSPLIT;
@@ -236,8 +215,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
   int ccq[PD];
   float nk[NOL ? PD : 1][16];       // NOL: the stage's BN scale / shift
 #define LOAD_STAGE(KS, J) do { \
-  conv_load_stage<MODE, FN, FM>(a, s_tab, KS, kgl, l16, n_base, pb, py, px, pv, base0, base1, ld0, ld1, wz, af[J], bq[J], \
-                                okq[J], ccq[J]); \
+  conv_load_stage<MODE, FN, FM>(a, s_tab, KS, kgl, l16, n_base, pb, py, px, pv, sb.base0, sb.base1, sb.ld0, sb.ld1, \
+                                sb.wz, af[J], bq[J], okq[J], ccq[J]); \
   if (NOL) nol_fetch(nk[NOL ? (J) : 0], ccq[J], s_nol, a.Cs); } while (0)
   // NOL: the operand transform runs when the stage is consumed, so the loads stay in flight meanwhile
 #define MMA_STAGE(J)                                                                                      \
@@ -321,19 +300,16 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = acc[i][f][r] + bias[r];
         if (nok && pv[f]) {
+          bf16_t* o = reinterpret_cast<bf16_t*>(a.out) + a.ogs * z + (int64_t)m * a.ldo + n0;
           if (is_fwd<MODE>()) {
-            bf16_t* o = reinterpret_cast<bf16_t*>(a.out) + a.ogs * z + (int64_t)m * a.ldo + n0;
-            uint2 w;
-            w.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-            w.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-            *reinterpret_cast<uint2*>(o) = w;
+            store4(o, v);
 #pragma unroll
             for (int r = 0; r < 4; ++r) { s[r] += v[r]; ss[r] += v[r] * v[r]; }
           } else {
-            bf16_t* o = reinterpret_cast<bf16_t*>(a.out) + a.ogs * z + (int64_t)m * a.ldo + n0;
             add_sources(a, z, (int64_t)m, n0, v);
             store4(o, v);
-            if (want_bnb && n0 < bN) {  // dz of the BN tail this gradient feeds, and its statistics
+            if (want_bnb && n0 < bN) {  // dz of the BN tail this gradient feeds, and its statistics (open-coded as
+                                        // in conv_tile.h tile_store: see the note there)
               const uint2 u = ypre[i][f], q = rpre[i][f];
               const float yv[4] = {__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u),
                                    __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u)};
@@ -367,44 +343,15 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
         }
       }
       if (want_red) {
+        const int cl = wn * WN + i * 16 + 4 * kgl;  // channel within the block tile
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {  // pixels of a 16-lane row -> lane 15 (DPP, common.h)
-          s[r] = row16_sum(s[r]);
-          ss[r] = row16_sum(ss[r]);
-          if (bres) s2[r] = row16_sum(s2[r]);
-        }
-        if (l16 == 15) {
-          const int cl = wn * WN + i * 16 + 4 * kgl;  // channel within the block tile
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            s_st[(wm * BN_T + cl + r) * 3 + 0] = s[r];
-            s_st[(wm * BN_T + cl + r) * 3 + 1] = ss[r];
-            s_st[(wm * BN_T + cl + r) * 3 + 2] = s2[r];
-          }
-        }
+        for (int r = 0; r < 4; ++r) stats_to_lds(s[r], ss[r], s2[r], bres, s_st + (wm * BN_T + cl + r) * 3, l16);
       }
     }
   }
   if (want_red) {
     __syncthreads();
-    const int rep = blk.x % (want_bnb ? a.bbn.pnrep : a.stats_nrep);
-    // forward: [G][NREP][2][N] (sum y, sum y^2); fused BN backward: rows 0/1 (2 with a BN2 residual) of
-    // the tail's [G][NREP][3][bN]
-    const int nrow = want_bnb ? (a.br_bn ? 3 : 2) : 2;
-    const int nlim = want_bnb ? bN : a.N;
-    const int64_t gb = want_bnb ? (a.bpgs < 0 ? (int64_t)z * NREP * 3 * bN : (int64_t)z * a.bpgs)
-                                : (int64_t)z * NREP * 2 * a.N;
-    double* dst = want_bnb ? a.bpart : a.stats;
-    for (int q = threadIdx.x; q < BN_T * 3; q += 256) {
-      const int cl = q / 3, which = q - cl * 3;
-      const int n = blk.y * BN_T + cl;
-      if (n < nlim && which < nrow) {
-        float v = 0.f;
-#pragma unroll
-        for (int w2 = 0; w2 < WAVES_M; ++w2) v += s_st[(w2 * BN_T + cl) * 3 + which];
-        atomicAdd(dst + gb + ((int64_t)rep * (want_bnb ? 3 : 2) + which) * nlim + n, (double)v);
-      }
-    }
+    stats_publish<want_bnb, BN_T, WAVES_M>(a, z, blk.x, blk.y * BN_T, bN, s_st);
   }
   ptick(a.ptm, 3);
 }
@@ -479,17 +426,7 @@ struct WgStage {
       if (v < VX) {
         const int p = v / (TK / 8), g = v - p * (TK / 8);
         uint4 u = rx[i];
-        if (a.nol && ((rok >> i) & 1)) {
-          uint32_t w4[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-          for (int h = 0; h < 4; ++h) {
-            float lo = __uint_as_float(w4[h] << 16) * s_nsc[g * 8 + 2 * h] + s_nsh[g * 8 + 2 * h];
-            float hi = __uint_as_float(w4[h] & 0xffff0000u) * s_nsc[g * 8 + 2 * h + 1] + s_nsh[g * 8 + 2 * h + 1];
-            if (a.nol_kind == ACT_RELU) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }
-            w4[h] = (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
-          }
-          u = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-        }
+        if (a.nol && ((rok >> i) & 1)) u = nol8(u, s_nsc + g * 8, s_nsh + g * 8, a.nol_kind == ACT_RELU);
         *reinterpret_cast<uint4*>(&s_x[p * ldx + g * 8]) = u;
       }
     }
@@ -791,18 +728,7 @@ DEV void wgrad_patch_block(const WgradArgs& a, const int tile, const int split, 
         const int cg = v % (CB / 8), q = v / (CB / 8);
         const int j = q / wpr, c = q - j * wpr;
         uint4 u = rp[i];
-        if (a.nol && ((pok >> i) & 1)) {
-          uint32_t w4[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-          for (int h = 0; h < 4; ++h) {
-            const int cc = cg * 8 + 2 * h;
-            float lo = __uint_as_float(w4[h] << 16) * s_nsc[cc] + s_nsh[cc];
-            float hi = __uint_as_float(w4[h] & 0xffff0000u) * s_nsc[cc + 1] + s_nsh[cc + 1];
-            if (a.nol_kind == ACT_RELU) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }
-            w4[h] = (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
-          }
-          u = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-        }
+        if (a.nol && ((pok >> i) & 1)) u = nol8(u, s_nsc + cg * 8, s_nsh + cg * 8, a.nol_kind == ACT_RELU);
         *reinterpret_cast<uint4*>(&s_p[(j * WP + c) * CBP + cg * 8]) = u;
       }
     }

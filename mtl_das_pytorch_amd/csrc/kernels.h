@@ -89,7 +89,7 @@ struct LdsPhase {
   int m0;   // first blockIdx.x of the phase
   int Kp;   // nh * nw * Cs padded to the K chunk
 };
-// Strip plan of a patch conv launch (conv_lds.hip conv_patch_kernel): R output rows per block, nstrip strips
+// Strip plan of a patch conv launch (conv_patch.hip conv_patch_kernel): R output rows per block, nstrip strips
 // per image, nslice channel slices; source pixel of strip element (j, q) = (oh0 + dy0 + j, dx0 + q).
 struct PatchPlan {
   int R, nstrip, nslice, Hout, Wout, dy0, dx0;
@@ -268,7 +268,7 @@ constexpr int CONV_LDS_CFG0 = 16, CONV_LDS_NCFG = 64;
 constexpr int CONV_DEEP_CFG0 = 128, CONV_DEEP_NCFG = 14;
 // LDS-DMA implicit GEMM (conv_lds.hip conv_glds_kernel): cfg = CONV_GLDS_CFG0 + 4 * tile + log2(splits)
 constexpr int CONV_GLDS_CFG0 = 160, CONV_GLDS_NCFG = 32;
-// patch conv for 3x3 / stride-1 layers (conv_lds.hip conv_patch_kernel): cfg = CONV_PATCH_CFG0 + 3 * tile + cb
+// patch conv for 3x3 / stride-1 layers (conv_patch.hip conv_patch_kernel): cfg = CONV_PATCH_CFG0 + 3 * tile + cb
 // (tile: BM x BN of PT_BM / PT_BN, cb: channel slice 16 / 32 / 64)
 constexpr int CONV_PATCH_CFG0 = 192, CONV_PATCH_NCFG = 15;
 // deep-ring LDS-DMA configs (conv_glds_kernel with up to 8 stages): cfg = CONV_GDEEP_CFG0 + 4 * tile + log2(splits)
@@ -277,7 +277,15 @@ constexpr int CONV_GDEEP_CFG0 = 208, CONV_GDEEP_NCFG = 32;
 constexpr int CONV_PATCHP_CFG0 = 240, CONV_PATCHP_NCFG = 15;
 // cfg flag of any conv config: launch it in XCD-contiguous tile order (ConvArgs::xcd, common.h block_coords)
 constexpr int CONV_XCD = 4096;
+// every LDS-staged config (mode: the kernel mode, MODE_FWD_NOL / MODE_DGRAD_BNS resolved); patch configs go on to
+// launch_conv_patch
 int launch_conv_lds(int mode, const ConvArgs& a, int G, int cfg, hipStream_t st);
+inline bool conv_patch_cfg(int cfg) {
+  return (cfg >= CONV_PATCH_CFG0 && cfg < CONV_PATCH_CFG0 + CONV_PATCH_NCFG) ||
+         (cfg >= CONV_PATCHP_CFG0 && cfg < CONV_PATCHP_CFG0 + CONV_PATCHP_NCFG);
+}
+int launch_conv_patch(int mode, const ConvArgs& a, int G, int cfg, hipStream_t st);  // conv_patch.hip
+int conv_patch_check(int mode, const ConvArgs& a, int cfg);  // 0, or < 0: the patch cfg cannot take this conv
 // fp32 workspace floats and ticket count a cfg needs (0 when it does not split K); < 0: cfg invalid for a
 int conv_lds_workspace(int mode, const ConvArgs& a, int G, int cfg, int64_t& ws_floats, int64_t& ntickets);
 int launch_wgrad(const WgradArgs& a, int G, int cfg, hipStream_t st);
