@@ -4,6 +4,7 @@
     python infer.py --model MTL --model_path run/<...>.pth --recording fiber.npy --stride 100,125 \
         --out predictions.csv --cell 50,125 --map maps.npz
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 infer.py ...   # windows sharded over ranks
+    python infer.py ... --chunk 2000 [--ring 4096]   # read and evaluate the recording 2000 time samples at a time
 """
 import argparse
 import os
@@ -25,6 +26,10 @@ def main():
     ap.add_argument("--out", default="predictions.csv")
     ap.add_argument("--cell", default=None, help="map cell (fiber, time) in samples; default: the stride")
     ap.add_argument("--map", default=None, help="write the event / distance maps of the recording to this .npz")
+    ap.add_argument("--chunk", type=int, default=None,
+                    help="feed the recording to a LiveRecording in chunks of this many time samples (a .npy is "
+                         "memory-mapped): the recording need not fit on the device; same CSV and maps")
+    ap.add_argument("--ring", type=int, default=None, help="with --chunk: time samples kept on the device")
     args = ap.parse_args()
 
     from mtl_das_pytorch_amd import use_engine_graph_queues
@@ -46,13 +51,23 @@ def main():
     model = build_model(args.model, in_channels=args.in_channels)
     if args.model_path:
         model.load_state_dict(torch.load(args.model_path, map_location="cpu", weights_only=True), strict=True)
-    if args.recording.endswith(".mat"):
-        rec = np.asarray(load_mat(args.recording, (args.key,)), dtype=np.float32)
-    else:
-        rec = np.load(args.recording, allow_pickle=False).astype(np.float32)
     use_engine = {"auto": None, "engine": True, "torch": False}[args.backend]
-    res = predict_recording(model, args.model, torch.from_numpy(rec), stride=stride, batch=args.batch_size, ctx=ctx,
-                            use_engine=use_engine)
+    live_maps = None
+    if args.chunk is not None:
+        if args.chunk < 1:
+            ap.error("--chunk must be positive")
+        if args.recording.endswith(".mat"):
+            rec = np.asarray(load_mat(args.recording, (args.key,)), dtype=np.float32)
+        else:
+            rec = np.load(args.recording, mmap_mode="r", allow_pickle=False)
+        res, live_maps = live_run(model, args, rec, stride, cell if args.map else None, ctx, use_engine)
+    else:
+        if args.recording.endswith(".mat"):
+            rec = np.asarray(load_mat(args.recording, (args.key,)), dtype=np.float32)
+        else:
+            rec = np.load(args.recording, allow_pickle=False).astype(np.float32)
+        res = predict_recording(model, args.model, torch.from_numpy(rec), stride=stride, batch=args.batch_size,
+                                ctx=ctx, use_engine=use_engine)
     if ctx.is_main:
         import pandas as pd
         cols = {"fiber_start": res["positions"][:, 0], "time_start": res["positions"][:, 1]}
@@ -63,17 +78,48 @@ def main():
         print(f"{len(res['positions'])} windows -> {args.out}")
         if args.map:
             shape = rec.shape[-2:]
-            fs, ts = window_starts(shape[0], WINDOW[0], stride[0]), window_starts(shape[1], WINDOW[1], stride[1])
-            probs = res["joint_prob"] if "joint_prob" in res else np.concatenate(
-                [res[k] for k in ("distance_prob", "event_prob") if k in res], 1)
-            if ctx.device.type == "cuda" and use_engine is not False:  # summed on the device; numpy fp64 otherwise
-                probs = torch.from_numpy(probs).to(ctx.device)
-            maps = prediction_map(probs, fs, ts, shape, cell)
+            if live_maps is not None:
+                maps = live_maps
+            else:
+                fs = window_starts(shape[0], WINDOW[0], stride[0])
+                ts = window_starts(shape[1], WINDOW[1], stride[1])
+                probs = res["joint_prob"] if "joint_prob" in res else np.concatenate(
+                    [res[k] for k in ("distance_prob", "event_prob") if k in res], 1)
+                if ctx.device.type == "cuda" and use_engine is not False:  # summed on the device; numpy fp64 otherwise
+                    probs = torch.from_numpy(probs).to(ctx.device)
+                maps = prediction_map(probs, fs, ts, shape, cell)
             nfc, ntc = next(iter(maps.values())).shape[-2:]
             np.savez(args.map, fiber_edges=np.minimum(np.arange(nfc + 1) * cell[0], shape[0]),
                      time_edges=np.minimum(np.arange(ntc + 1) * cell[1], shape[1]), **maps)
             print(f"{nfc} x {ntc} cells -> {args.map}")
     shutdown(ctx)
+
+
+def live_run(model, args, rec, stride, cell, ctx, use_engine):
+    """The recording through a LiveRecording, ``--chunk`` time samples at a time: the result dict of
+    predict_recording (windows in its order) and, with ``cell``, the maps of prediction_map."""
+    import numpy as np
+    from mtl_das_pytorch_amd.inference import WINDOW, LiveRecording
+    rec3 = rec if rec.ndim == 3 else rec[None]
+    C, F, T = rec3.shape
+    ring = args.ring if args.ring is not None else max(8 * WINDOW[1], WINDOW[1] + min(args.chunk, 1 << 14))
+    live = LiveRecording(model, args.model, F, C=C, stride=stride, cell=cell, ring=ring, batch=args.batch_size,
+                         ctx=ctx, use_engine=use_engine)
+    outs = []
+    for t in range(0, T, args.chunk):
+        outs.append(live.push(np.ascontiguousarray(rec3[:, :, t:t + args.chunk], dtype=np.float32)))
+    outs.append(live.flush())
+    live.close()
+    pos = np.concatenate([o["positions"] for o in outs])
+    if len(pos) == 0:
+        raise ValueError(f"recording dimension {T} is shorter than the window {WINDOW[1]}")
+    order = np.lexsort((pos[:, 1], pos[:, 0]))  # fiber-major, as the whole-recording table
+    res = {k: np.concatenate([o[k] for o in outs])[order] for k in outs[0] if k != "map_columns"}
+    maps = None
+    if cell is not None:
+        maps = {k: np.concatenate([o["map_columns"][k] for o in outs], -1)
+                for k in outs[0]["map_columns"] if k not in ("first", "last", "class_map")}
+    return res, maps
 
 
 if __name__ == "__main__":

@@ -425,6 +425,46 @@ void window_map(int64_t stream, py::dict d, std::vector<int> fs, std::vector<int
   check(launch_window_map(a, fs.data(), ts.data(), S(stream)), "window_map");
 }
 
+LiveArgs parse_live(const py::dict& d) {
+  LiveArgs a{};
+  a.ring = P<float>(d, "ring"); a.fs = P<const int>(d, "fs"); a.state = P<int64_t>(d, "state");
+  a.C = (int)I(d, "C"); a.F = (int)I(d, "F"); a.R = (int)I(d, "R"); a.nf = (int)I(d, "nf"); a.st = (int)I(d, "st");
+  a.B = (int)I(d, "B"); a.Wf = (int)I(d, "Wf"); a.Wt = (int)I(d, "Wt");
+  a.taps = (int)I(d, "taps"); a.off = (int)I(d, "off");
+  return a;
+}
+
+void ring_append(int64_t stream, py::dict d) {
+  check(launch_ring_append(parse_live(d), P<const float>(d, "chunk"), (int)I(d, "n"), (int)I(d, "flush"), S(stream)),
+        "ring_append");
+}
+
+void gather_windows_ring(int64_t stream, py::dict d) {
+  check(launch_gather_windows_ring(parse_live(d), P<bf16_t>(d, "out"), P<int64_t>(d, "lab_out"), (int)I(d, "lab_w"),
+                                   S(stream)), "gather_windows_ring");
+}
+
+void live_probs(int64_t stream, py::dict d) {
+  std::vector<int> ncls;
+  if (d.contains("ncls")) ncls = d["ncls"].cast<std::vector<int>>();
+  if (ncls.size() > 4) throw std::runtime_error("live_probs: at most 4 tasks");
+  check(launch_live_probs(parse_live(d), P<const float>(d, "src"), (int)I(d, "softmax"), (int)ncls.size(),
+                          ncls.data(), (int)I(d, "K"), P<float>(d, "table"), I(d, "nrows"), (int)I(d, "Jcap"),
+                          S(stream)), "live_probs");
+}
+
+void live_map(int64_t stream, py::dict d, std::vector<int> fs, std::vector<int64_t> jlo, std::vector<int> jn) {
+  LiveMapArgs a{};
+  a.table = P<const float>(d, "table"); a.fs = P<const int>(d, "fs"); a.map = P<float>(d, "map");
+  a.wf = P<const float>(d, "wf"); a.wt = P<const float>(d, "wt");
+  a.jlo = P<const int64_t>(d, "jlo"); a.jn = P<const int>(d, "jn");
+  a.mf = (int)I(d, "mf"); a.mw = (int)I(d, "mw"); a.nf = (int)fs.size(); a.K = (int)I(d, "K"); a.F = (int)I(d, "F");
+  a.Wf = (int)I(d, "Wf"); a.cf = (int)I(d, "cf"); a.nfc = (int)I(d, "nfc"); a.ncol = (int)jlo.size();
+  a.Jcap = (int)I(d, "Jcap");
+  if (jn.size() != jlo.size()) throw std::runtime_error("live_map: jlo and jn differ in length");
+  check(launch_live_map(a, I(d, "nrows"), fs.data(), jlo.data(), jn.data(), S(stream)), "live_map");
+}
+
 void pool3(int is_max, int backward, int64_t stream, py::dict d) {
   PoolArgs a{};
   a.x = P<const bf16_t>(d, "x"); a.ldx = (int)I(d, "ldx");
@@ -557,6 +597,10 @@ PYBIND11_MODULE(_mda_hip, m) {
   m.def("gather_windows", &gather_windows);
   m.def("window_probs", &window_probs);
   m.def("window_map", &window_map, py::arg("stream"), py::arg("d"), py::arg("fs"), py::arg("ts"));
+  m.def("ring_append", &ring_append);
+  m.def("gather_windows_ring", &gather_windows_ring);
+  m.def("live_probs", &live_probs);
+  m.def("live_map", &live_map, py::arg("stream"), py::arg("d"), py::arg("fs"), py::arg("jlo"), py::arg("jn"));
   m.def("wgrad_table", &wgrad_table);
   m.def("wgrad_batched", &wgrad_batched, py::arg("cfg"), py::arg("table"), py::arg("nj"), py::arg("nblocks"),
         py::arg("stream"), py::arg("cap") = 0);

@@ -369,6 +369,40 @@ struct MapArgs {
 };
 // h_fs / h_ts: host copies of the start tables, checked to cover [0, F) x [0, T) (-2 otherwise)
 int launch_window_map(const MapArgs& a, const int* h_fs, const int* h_ts, hipStream_t st);
+// live.hip: inference on a growing recording -- the time axis as a ring of R columns, windows numbered time-major
+// (n = j * nf + a: time index j starts at j * st), probabilities into a ring table, final map columns
+enum { LIVE_TOTAL = 0, LIVE_AVAIL, LIVE_NEXT, LIVE_JEND, LIVE_TEND, LIVE_NSTATE };
+struct LiveArgs {
+  float* ring;        // [C][F][R] fp32: time sample t at column t mod R
+  const int* fs;      // window starts along the fiber [nf]
+  // device scalars [LIVE_NSTATE]: total = time samples received; avail = window numbers that can be evaluated;
+  // next = the first window number not evaluated yet (batch row r holds window next + r, padding from avail on);
+  // jend / tend = number and start of the end-aligned time index (jend = -1 until the stream is flushed)
+  int64_t* state;
+  int C, F, R, nf, st;
+  int B, Wf, Wt;      // batch rows, window size
+  int taps, off;      // vertical tap packing of a 1-channel stem (gather_batch)
+};
+// chunk [C][F][n] (n <= R - Wt) -> ring, total += n, avail from the new total; flush: the stream ends at the new
+// total (n may be 0) and the end-aligned index, if there is one, becomes available.  -2 on bad arguments, as below.
+int launch_ring_append(const LiveArgs& a, const float* chunk, int n, int flush, hipStream_t st);
+int launch_gather_windows_ring(const LiveArgs& a, bf16_t* out, int64_t* lab_out, int lab_w, hipStream_t st);
+// launch_window_probs' two forms; table [nrows][K], nrows >= Jcap * nf; advances next by the valid rows
+int launch_live_probs(const LiveArgs& a, const float* src, int softmax, int T, const int* ncls, int K, float* table,
+                      int64_t nrows, int Jcap, hipStream_t st);
+struct LiveMapArgs {
+  const float* table;  // ring table [Jcap * nf][K]
+  const int* fs;       // device copy of the fiber start table
+  float* map;          // [K][nfc][ncol]: the cell columns q0 .. q0 + ncol - 1
+  const float* wf;     // fiber weight bands [nf][mf], as MapArgs
+  const float* wt;     // [ncol][mw]: weights of column q's time indices jlo[q] .. jlo[q] + jn[q] - 1
+  const int64_t* jlo;  // [ncol]
+  const int* jn;       // [ncol]
+  int mf, mw, nf, K, F, Wf, cf, nfc, ncol, Jcap;
+};
+// h_*: host copies of fs / jlo / jn, checked (fs covers [0, F); 1 <= jn <= min(mw, Jcap); jlo >= 0)
+int launch_live_map(const LiveMapArgs& a, int64_t nrows, const int* h_fs, const int64_t* h_jlo, const int* h_jn,
+                    hipStream_t st);
 // synth.hip: on-device synthetic DAS samples (data/synthetic.py physical model, Philox noise)
 constexpr int SYNTH_NPARAM = 9;  // per sample: distance, event, x0, t0, jitter[4], snr_db
 struct SynthArgs {

@@ -16,6 +16,7 @@ from .program import (COMM_STREAM, SPILL_STREAM, Launch, Phase, k_adam, k_step_i
                       k_tail_fwd_batched, k_wgfin, k_wgrad,
                       k_wgrad_batched, k_window_probs)
 from .program import NoiseSpec, k_gather_noise, k_noise_advance
+from .program import k_gather_windows_ring, k_live_probs
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID, SIGMUL, ADD_RELU, POOL_RELU = range(6)
 
@@ -486,6 +487,55 @@ class LoweredProgram:
         ph = Phase("window_probs")
         ph.add("window_probs", k_window_probs, d)
         ph.keep = (probs, idx, cursor)
+        return ph
+
+    @staticmethod
+    def _live_state_ok(state):
+        if state.dtype != torch.int64 or not state.is_cuda or not state.is_contiguous() or state.numel() != 5:
+            raise ValueError("the live scalars must be a contiguous int64 [5] tensor on the device (live_state)")
+
+    def live_gather_phase(self, ring, fs, state, st: int) -> Phase:
+        """The batch gather of live inference: the batch's (H0, W0) windows are cut from the time ring ``ring``
+        ([C, F, R] fp32 on the device, sample t at column t mod R) into the stem's input, labels zeroed.  Batch row
+        ``r`` is window ``next + r`` = ``(j, a)`` -- fiber start ``fs[a]`` (int32 device table), time start
+        ``j * st`` -- while that is below ``avail``; the other rows are zeros (``state``: the device scalars of
+        ops.functional.live_state, advanced by ring_append and live_probs_phase)."""
+        if ring.dim() != 3 or ring.dtype != torch.float32 or not ring.is_contiguous() or not ring.is_cuda:
+            raise ValueError("ring must be a contiguous fp32 [C, F, R] tensor on the device")
+        if self.stem_pack[0] and ring.shape[0] != 1:
+            raise ValueError("stem tap packing needs a single-channel input")
+        if fs.dtype != torch.int32 or fs.dim() != 1 or not fs.is_contiguous() or not fs.is_cuda:
+            raise ValueError("the fiber window-start table must be a contiguous int32 vector on the device")
+        if ring.shape[2] < self.W0 + 1:
+            raise ValueError(f"a ring of {ring.shape[2]} time columns is below the window's {self.W0} + 1")
+        self._live_state_ok(state)
+        d = {"ring": P(ring), "fs": P(fs), "state": P(state), "C": ring.shape[0], "F": ring.shape[1],
+             "R": ring.shape[2], "nf": fs.numel(), "st": int(st), "B": self.B, "Wf": self.H0, "Wt": self.W0,
+             "taps": self.stem_pack[0], "off": self.stem_pack[1], "out": P(self.x), "lab_out": P(self.labels),
+             "lab_w": self.label_width}
+        ph = Phase("live_gather")
+        ph.add("gather_windows_ring", k_gather_windows_ring, d)
+        ph.keep = (ring, fs, state)  # the launch holds their device pointers
+        return ph
+
+    def live_probs_phase(self, table, state, nf: int, jcap: int) -> Phase:
+        """After ``fwd_eval``: the valid batch rows' probabilities into the ring table ``table`` [>= jcap * nf, K]
+        at row ``(j mod jcap) * nf + a``; the launch then advances ``next`` by the number of valid rows."""
+        ncls = self.prob_classes()
+        if (table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous() or not table.is_cuda
+                or table.shape[1] != sum(ncls)):
+            raise ValueError(f"probability table must be a contiguous fp32 [N, {sum(ncls)}] tensor on the device")
+        if jcap < 1 or nf < 1 or table.shape[0] < jcap * nf:
+            raise ValueError(f"a table of {table.shape[0]} rows is below jcap * nf = {jcap * nf}")
+        self._live_state_ok(state)
+        softmax = self.logp.dim() == 2
+        d = {"state": P(state), "B": self.B, "nf": int(nf), "src": P(self.logp), "softmax": int(softmax),
+             "K": table.shape[1], "table": P(table), "nrows": table.shape[0], "Jcap": int(jcap)}
+        if not softmax:
+            d["ncls"] = ncls
+        ph = Phase("live_probs")
+        ph.add("live_probs", k_live_probs, d)
+        ph.keep = (table, state)
         return ph
 
     def _wgfin_args(self, convs=None):

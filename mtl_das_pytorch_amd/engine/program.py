@@ -425,3 +425,13 @@ def k_gather_windows(d, st):
 def k_window_probs(d, st):
     """The batch's probabilities into the resident table; in cursor form it advances the batch cursor."""
     lib().window_probs(st, d)
+
+
+def k_gather_windows_ring(d, st):
+    """The batch's windows cut from the time ring of a live recording (csrc/live.hip)."""
+    lib().gather_windows_ring(st, d)
+
+
+def k_live_probs(d, st):
+    """The batch's probabilities into the live ring table; advances the window counter by the valid rows."""
+    lib().live_probs(st, d)

@@ -29,6 +29,13 @@ An inference step over a resident recording (set_window_source / infer_step) is
 
 one graph too: the batch's windows are numbered by a device cursor that the step's last kernel advances, so the
 replays that cover a recording need no host copy between them.
+
+A live step over a growing recording (set_live_source / live_step) is the same graph over a time ring:
+
+    [ring gather of windows next .. next + B - 1] [eval forward] [probabilities -> ring table, next += valid rows]
+
+The ring, the counters and the table are device state that ring_append and the graph advance, so one capture serves
+every push of the stream; ``captures`` counts the captures of a runner.
 """
 from __future__ import annotations
 
@@ -109,6 +116,8 @@ class StepRunner:
         self.window = None  # resident-recording inference (set_window_source): (rec, fs, ts, probs, lo, hi)
         self.window_cursor = None
         self.window_key = None  # what the source's owner knows it by (inference.resident_probs: shape and starts)
+        self.live = None  # live inference (set_live_source): (ring, fs, state, table, st, jcap)
+        self.captures = 0  # graphs captured so far (a live source is captured once, whatever is pushed)
         # SNR noise in the gather (set_train_noise / set_eval_noise): per mode the launch constant (seed; None: off)
         # and the device scalars the captured graphs read -- fp32 (lo, hi) and the int64 draw number
         self.noise_seed = {"train": None, "eval": None}
@@ -198,6 +207,8 @@ class StepRunner:
         # the inference step advances its batch cursor and fills rows of the probability table: a warm-up that
         # left either behind would skip the first batch
         infer = [self.window_cursor, self.window[3]] if kind == "infer" else []
+        if kind == "live":  # next / avail / total and the table: a warm-up may not consume windows
+            infer = [self.live[2], self.live[3]]
         return ([f.params, f.grads, f.exp_avg, f.exp_avg_sq, f.bn_mean, f.bn_var, f.bn_nbt, f.step, self.p.metrics,
                  self.p.confusion, self.p.logp] + list(self.p.extra_state)
                 + ([self.cursor] if self.cursor is not None else []) + infer
@@ -215,6 +226,11 @@ class StepRunner:
             rec, fs, ts, probs, lo, hi = self.window
             gather = p.window_gather_phase(rec, fs, ts, cursor=self.window_cursor, lo=lo, hi=hi)
             store = p.window_probs_phase(probs, cursor=self.window_cursor, lo=lo, hi=hi)
+            return [gather.run, p.fwd_eval.run, store.run]
+        if kind == "live":
+            ring, fs, state, table, st, jcap = self.live
+            gather = p.live_gather_phase(ring, fs, state, st)
+            store = p.live_probs_phase(table, state, fs.numel(), jcap)
             return [gather.run, p.fwd_eval.run, store.run]
         X, lab = self.sources["train" if kind.startswith("train") else "eval"]
         # a training step's gather also zeroes the arena's accumulators (one launch; arena.clear otherwise)
@@ -281,6 +297,7 @@ class StepRunner:
             torch.cuda.synchronize()
             self.graphs[kind] = g
             self.keepers[kind] = keeper
+            self.captures += 1
 
     # -------------------------------------------------------------------------------------------
     def set_lr(self, lr: float):
@@ -377,6 +394,42 @@ class StepRunner:
         if not self._packed:
             self.pack_weights()
         self._run("infer")
+
+    def set_live_source(self, ring: torch.Tensor, fs: torch.Tensor, state: torch.Tensor, table: torch.Tensor,
+                        st: int, jcap: int):
+        """Live inference on a growing recording: ``live_step()`` then evaluates windows ``next .. next + B - 1`` of
+        the time ring ``ring`` [C, F, R] -- window ``n = j * nf + a`` at ``(fs[a], j * st)``, those from ``avail`` on
+        as padding -- and writes their probabilities to rows ``(j mod jcap) * nf + a`` of ``table``; the step's last
+        kernel advances ``next`` by the valid rows.  ``state``: the device scalars (ops.functional.live_state) that
+        ring_append advances as data arrives.  The graph is captured once per source: pushes, the wrap of the ring
+        and the end of the stream only change device state."""
+        new = (ring, fs, state, table, int(st), int(jcap))
+        cur = self.live
+        if cur is None or any(a is not b for a, b in zip(cur[:4], new[:4])) or cur[4:] != new[4:]:
+            self.live = new
+            self._drop_graph("live")
+
+    def clear_live_source(self):
+        """Release the live source (its graph, and the runner's hold on the ring and the table)."""
+        self._drop_graph("live")
+        self.live = None
+
+    def prepare_live(self):
+        """Capture the live graph now (side effects rolled back), so that no push pays for it."""
+        if self.live is None:
+            raise ValueError("prepare_live() needs set_live_source")
+        if not self._packed:
+            self.pack_weights()
+        if self.use_graph:
+            self._ensure_graph("live")
+
+    def live_step(self):
+        """One batch of the live source: [ring gather, eval forward, probabilities + next], one graph."""
+        if self.live is None:
+            raise ValueError("live_step() needs set_live_source")
+        if not self._packed:
+            self.pack_weights()
+        self._run("live")
 
     def reset_metrics(self):
         self.p.metrics.zero_()

@@ -14,6 +14,10 @@ are cut on the device straight into the stem's input, the probabilities land in 
 graph, and the window stack -- (100 * 250) / (stride_f * stride_t) times the recording -- never exists.
 :func:`prediction_map` averages the overlapping windows' probabilities into an event-probability and distance
 map along the fiber over time.
+
+:class:`LiveRecording` serves a recording that is still growing: chunks of time samples go into a ring, the windows
+that became available are evaluated by replays of one graph, and map columns are returned as they become final
+(csrc/live.hip on the engine path, a host ring and the fp32 module elsewhere).
 """
 from __future__ import annotations
 
@@ -267,6 +271,11 @@ def prediction_map(res_or_probs, fs, ts, shape: Tuple[int, int], cell: Tuple[int
     else:
         table = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table
         m = window_map_reference(table, fs, ts, shape, cell, window)
+    return _task_maps(m)
+
+
+def _task_maps(m: np.ndarray) -> Dict:
+    """The event / distance maps of a class map [K, nfc, ntc] (K as :func:`prediction_map` lists them)."""
     K = m.shape[0]
     out = {}
     if K == 32:  # joint = distance + 16 * event
@@ -284,3 +293,382 @@ def prediction_map(res_or_probs, fs, ts, shape: Tuple[int, int], cell: Tuple[int
         d = np.arange(16, dtype=out["distance_map"].dtype)
         out["distance_mean_m"] = np.tensordot(d, out["distance_map"], 1)
     return out
+
+
+# ---- live inference on a growing recording -----------------------------------------------------------------------
+# The recording arrives as chunks [C, F, n] in time order.  Its time axis lives in a ring of R >= Wt + 1 columns
+# (sample t at column t mod R); time index j = 0, 1, ... starts at j * st and window (j, a) has the number
+# n = j * nf + a -- time-major, so new windows append at the end -- and is evaluated once j * st + Wt <= total.
+# flush() ends the stream at T = total and adds the end-aligned index of window_starts if (T - Wt) mod st != 0.
+# Cell column q of the map is final once (q + 1) * ct <= total - Wt: every regular window covering it has run, and
+# the end-aligned window of any possible end starts at or after total - Wt.
+
+
+def live_time_weights(q: int, ct: int, Wt: int, st: int, T: Optional[int] = None) -> Tuple[int, np.ndarray]:
+    """``(jlo, w)``: the time indices ``jlo .. jlo + len(w) - 1`` that cover cell column ``q`` and their fp64 weights
+    (:func:`ops.functional.window_cell_weights` of the time axis at that column, without the whole table).  ``T``
+    None: the stream is still running and the column is final, so only regular indices cover it; otherwise the
+    stream ended at ``T`` and the end-aligned index, if there is one, is the last regular index + 1."""
+    c0 = q * ct
+    c1 = c0 + ct if T is None else min(c0 + ct, T)
+    if c1 <= c0:
+        raise ValueError(f"cell column {q} is outside the recording")
+    t = np.arange(c0, c1, dtype=np.int64)
+    jl = np.maximum(0, -((Wt - 1 - t) // st))  # first regular index with j * st + Wt > t
+    jh = t // st                               # last regular index with j * st <= t
+    last = int(jh.max())
+    end = np.zeros(len(t), dtype=bool)
+    if T is not None:
+        if T < Wt:
+            raise ValueError(f"recording dimension {T} is shorter than the window {Wt}")
+        nreg = (T - Wt) // st + 1
+        jh = np.minimum(jh, nreg - 1)
+        last = int(jh.max())
+        if (T - Wt) % st != 0 and c1 > T - Wt:
+            end = t >= T - Wt
+            last = nreg
+    cover = jh - jl + 1 + end
+    if (cover <= 0).any():
+        raise ValueError("the window starts do not cover the recording")
+    inv = 1.0 / cover
+    jlo = int(jl.min())
+    w = np.zeros(last - jlo + 1)
+    for j in range(jlo, last + 1):
+        sel = end if (end.any() and j == last) else (jl <= j) & (j <= jh)
+        w[j - jlo] = inv[sel].sum() / (c1 - c0)
+    return jlo, w
+
+
+class LiveBook:
+    """The host's integer arithmetic of a live recording: how many time indices can be evaluated and how many cell
+    columns are final at a given total, how ``push`` splits a chunk, and how many rows of the ring table are alive.
+    It mirrors the device's scalars (csrc/live.hip ring_advance_kernel) and never reads them."""
+
+    def __init__(self, Wt: int, st: int, ring: int, ct: Optional[int] = None, table_indices: Optional[int] = None):
+        if ring < Wt + 1:
+            raise ValueError(f"a ring of {ring} time columns is below the window's {Wt} + 1")
+        if st < 1 or (ct is not None and ct < 1):
+            raise ValueError("stride and cell must be positive")
+        self.Wt, self.st, self.R, self.ct = int(Wt), int(st), int(ring), ct
+        # a sub-chunk adds at most (R - Wt) // st + 1 indices; a non-final column reaches back (Wt + ct) // st + 2
+        carried = (self.Wt + ct) // self.st + 2 if ct is not None else 0
+        self.jcap = int(table_indices) if table_indices is not None else (self.R - self.Wt) // self.st + 1 + carried
+        if self.jcap < 1:
+            raise ValueError("the table needs at least one time index")
+        self.total = 0     # time samples received
+        self.j_done = 0    # time indices evaluated
+        self.q_done = 0    # cell columns emitted
+        self.jend = None   # (number, start) of the end-aligned index, once flushed
+        self.flushed = False
+
+    def indices(self, total: int) -> int:
+        return (total - self.Wt) // self.st + 1 if total >= self.Wt else 0
+
+    def final_columns(self, total: int) -> int:
+        return (total - self.Wt) // self.ct if (self.ct is not None and total >= self.Wt) else 0
+
+    def first_needed(self) -> int:
+        """The oldest time index whose table rows a column not yet emitted still reads."""
+        if self.ct is None:
+            return self.j_done
+        return min(self.j_done, max(0, (self.q_done * self.ct - self.Wt) // self.st + 1))
+
+    def split(self, n: int):
+        """The sizes ``push`` appends a chunk of ``n`` samples in: at most R - Wt each, so the data of the oldest
+        window not yet evaluated (it starts after total - Wt) survives the append."""
+        step = self.R - self.Wt
+        return [min(step, n - i) for i in range(0, n, step)]
+
+    def time_start(self, j: int) -> int:
+        return self.jend[1] if (self.jend is not None and j == self.jend[0]) else j * self.st
+
+    def _check_table(self, j1: int, oldest: int):
+        if j1 - oldest > self.jcap:
+            raise ValueError(f"the probability table holds {self.jcap} time indices, this push needs {j1 - oldest} "
+                             "(its own and those that non-final map columns still read): a smaller chunk, a larger "
+                             "ring or table_indices")
+
+    def check_push(self, n: int):
+        """Raise before anything is written if a step of this push would overwrite live rows of the table."""
+        if self.flushed:
+            raise RuntimeError("push after flush")
+        total, j_done, q_done = self.total, self.j_done, self.q_done
+        try:
+            for m in self.split(n):
+                self.advance(m)
+        finally:
+            self.total, self.j_done, self.q_done = total, j_done, q_done
+
+    def advance(self, n: int):
+        """Append ``n <= R - Wt`` samples: returns the time indices ``[j0, j1)`` to evaluate and the cell columns
+        ``[q0, q1)`` that become final."""
+        if self.flushed:
+            raise RuntimeError("push after flush")
+        if not 1 <= n <= self.R - self.Wt:
+            raise ValueError(f"an append of {n} samples; 1 .. R - Wt = {self.R - self.Wt}")
+        total = self.total + n
+        j0, j1 = self.j_done, self.indices(total)
+        self._check_table(j1, self.first_needed())
+        q0, q1 = self.q_done, max(self.q_done, self.final_columns(total))
+        self.total, self.j_done, self.q_done = total, j1, q1
+        return (j0, j1), (q0, q1)
+
+    def finish(self):
+        """End the stream at T = total: the end-aligned index (if any) and every remaining column."""
+        if self.flushed:
+            raise RuntimeError("flush after flush")
+        T = self.total
+        j0 = j1 = self.j_done
+        q0 = q1 = self.q_done
+        if T >= self.Wt:
+            if (T - self.Wt) % self.st != 0:
+                j1 = j0 + 1
+                self._check_table(j1, self.first_needed())
+                self.jend = (j0, T - self.Wt)
+            if self.ct is not None:
+                q1 = -(-T // self.ct)
+        self.flushed = True
+        self.j_done, self.q_done = j1, q1
+        return (j0, j1), (q0, q1)
+
+
+def _task_names(model, model_type: str):
+    names = {"MTL": ["distance", "event"], "single_distance": ["distance"], "single_event": ["event"],
+             "multi_classifier": ["joint"]}[model_type]
+    ncls = {"distance": 16, "event": 2, "joint": model.num_classes if model_type == "multi_classifier" else 0}
+    return names, [ncls[t] for t in names]
+
+
+class _TorchLive:
+    """The torch backend of :class:`LiveRecording`: a host (or ``device``) ring and table, the module in fp32."""
+
+    def __init__(self, model, model_type, C, F, R, fs, window, st, jcap, K, batch, device):
+        self.model, self.model_type, self.batch, self.device = model.eval().to(device), model_type, batch, device
+        self.fs, self.window, self.st, self.jcap, self.R = fs, window, st, jcap, R
+        self.ring = torch.full((C, F, R), float("nan"))
+        self.table = np.full((jcap * len(fs), K), np.nan, dtype=np.float32)
+        self.total = 0
+
+    def append(self, chunk: torch.Tensor):
+        n = chunk.shape[2]
+        cols = (self.total + torch.arange(n)) % self.R
+        self.ring[:, :, cols] = chunk.detach().to("cpu", torch.float32)
+        self.total += n
+
+    def flush(self):
+        pass
+
+    def evaluate(self, starts) -> np.ndarray:
+        """``starts``: [(j, t0)].  Evaluates the windows (j, a) in number order; returns their rows [m * nf, K]."""
+        nf, (Wf, Wt) = len(self.fs), self.window
+        if not starts:
+            return np.zeros((0, self.table.shape[1]), dtype=np.float32)
+        tiles = []
+        for j, t0 in starts:
+            cols = (t0 + torch.arange(Wt)) % self.R
+            for f0 in self.fs:
+                tiles.append(self.ring[:, int(f0):int(f0) + Wf][:, :, cols])
+        x = torch.stack(tiles)
+        rows = []
+        for i in range(0, len(x), self.batch):
+            ps = _torch_probs(self.model, self.model_type, x[i:i + self.batch].to(self.device))
+            rows.append(torch.cat([p.float() for p in ps], 1).cpu())
+        rows = torch.cat(rows).numpy()
+        for k, (j, _) in enumerate(starts):
+            r = (j % self.jcap) * nf
+            self.table[r:r + nf] = rows[k * nf:(k + 1) * nf]
+        return rows
+
+    def map_columns(self, wf: np.ndarray, cols) -> np.ndarray:
+        """fp64 [K, nfc, ncol]; ``wf``: fp64 [nf, nfc]; ``cols``: [(jlo, w)] per column."""
+        nf = len(self.fs)
+        out = np.zeros((self.table.shape[1], wf.shape[1], len(cols)))
+        for q, (jlo, w) in enumerate(cols):
+            rows = [(j % self.jcap) * nf for j in range(jlo, jlo + len(w))]
+            p = np.stack([self.table[r:r + nf] for r in rows]).astype(np.float64)  # [jn, nf, K]
+            out[:, :, q] = np.einsum("ai,j,jak->ki", wf, w, p)
+        return out
+
+    def close(self):
+        pass
+
+
+class _EngineLive:
+    """The engine backend: device ring, device scalars and ring table; one captured graph per live source."""
+
+    def __init__(self, model, model_type, C, F, R, fs, window, st, jcap, K, batch, device):
+        from .ops import functional as HF
+        if window != WINDOW:
+            raise ValueError(f"the lowered models take {WINDOW} windows")
+        self.HF, self.fs, self.window, self.st, self.jcap, self.R = HF, fs, window, st, jcap, R
+        self.runner = window_runner(model, model_type, batch, device)
+        self.B = self.runner.p.B
+        dev = self.runner.p.device
+        self.ring = torch.zeros(C, F, R, device=dev)
+        self.state = HF.live_state(dev)
+        self.table = torch.zeros(jcap * len(fs), K, device=dev)
+        self.fs_d = torch.as_tensor(np.asarray(fs), dtype=torch.int32).to(dev)
+        # one pinned staging buffer and its device twin, reused by every push
+        self.stage_h = torch.empty(C * F * (R - window[1]), dtype=torch.float32).pin_memory()
+        self.stage_d = torch.empty(C * F * (R - window[1]), dtype=torch.float32, device=dev)
+        self.staged = None  # event: the last upload from stage_h has finished
+        self.runner.set_live_source(self.ring, self.fs_d, self.state, self.table, st, jcap)
+        self.runner.prepare_live()  # the one capture
+
+    def append(self, chunk: torch.Tensor):
+        C, Fn, n = chunk.shape
+        dst = self.stage_d[:C * Fn * n].view(C, Fn, n)
+        if chunk.is_cuda:
+            dst.copy_(chunk)
+        else:
+            if self.staged is not None:
+                self.staged.synchronize()  # the buffer is being read until then
+            src = self.stage_h[:C * Fn * n].view(C, Fn, n)
+            src.copy_(chunk)
+            dst.copy_(src, non_blocking=True)
+            self.staged = torch.cuda.Event()
+            self.staged.record()
+        self.HF.ring_append(self.ring, self.state, dst, len(self.fs), self.st, self.window[1])
+
+    def flush(self):
+        self.HF.ring_append(self.ring, self.state, None, len(self.fs), self.st, self.window[1], flush=True)
+
+    def evaluate(self, starts) -> np.ndarray:
+        nf = len(self.fs)
+        m = len(starts) * nf
+        if m == 0:
+            return np.zeros((0, self.table.shape[1]), dtype=np.float32)
+        for _ in range((m + self.B - 1) // self.B):
+            self.runner.live_step()
+        rows = torch.as_tensor([(j % self.jcap) * nf + a for j, _ in starts for a in range(nf)],
+                               dtype=torch.int64).to(self.table.device)
+        return self.table.index_select(0, rows).cpu().numpy()
+
+    def map_columns(self, wf, cols) -> np.ndarray:
+        F_ = self.ring.shape[1]
+        m = self.HF.live_map(self.table, self.fs, F_, self.window[0], self.cf, self.jcap, [c[0] for c in cols],
+                             [c[1] for c in cols])
+        return m.cpu().numpy().astype(np.float64)
+
+    def close(self):
+        if self.runner is not None:
+            self.runner.clear_live_source()
+            self.runner.close()
+            self.runner = None
+
+
+class LiveRecording:
+    """Sliding-window inference on a recording that is still growing.
+
+    ``push(chunk)`` takes the next ``[C, F, n]`` (or ``[F, n]``) time samples, on the CPU or the device, and returns
+    the predictions of the windows that became available -- ``positions`` [m, 2] and per task ``<task>_pred`` /
+    ``<task>_prob``, as :func:`predict_recording` -- in evaluation order (time-major).  With ``cell`` = (cf, ct) it
+    also returns ``map_columns``: ``first`` / ``last`` (one past) of the cell columns that became final and their
+    ``event_map`` / ``distance_map`` / ``distance_mean_m`` slices [.., nfc, last - first] (and ``class_map``, every
+    class of the probability table before the tasks are marginalised); a column is returned once
+    and never revised.  ``flush()`` ends the stream: the end-aligned window of :func:`window_starts` and every
+    remaining column.  Over all calls the windows are exactly those of ``predict_recording(rec, stride=stride)`` on
+    the concatenated chunks, and the columns those of :func:`prediction_map`.
+
+    ``ring``: time columns kept (>= window + 1); a chunk longer than ``ring - window`` is appended in pieces.
+    ``table_indices``: time indices the probability table holds (default: enough for any push); a push that would
+    overwrite rows still needed raises before it changes anything.  On the engine backend the ring, the window
+    counters and the table live on the device and every batch is one replay of one graph captured at construction
+    (``captures`` stays at 1); the torch backend keeps a host ring and evaluates the module in fp32."""
+
+    def __init__(self, model: nn.Module, model_type: str, F: int, C: int = 1, stride=(100, 125), cell=None,
+                 ring: int = 8 * WINDOW[1], batch: int = 32, device=None, use_engine: Optional[bool] = None,
+                 ctx: Optional[DistContext] = None, table_indices: Optional[int] = None, window=WINDOW):
+        if ctx is not None and ctx.enabled and ctx.world > 1:
+            raise ValueError("a live recording is not sharded: world > 1 is not supported")
+        device = torch.device(device) if device is not None else (ctx.device if ctx else torch.device("cpu"))
+        if use_engine is None:
+            use_engine = device.type == "cuda"
+        self.model_type, self.F, self.C, self.window = model_type, int(F), int(C), tuple(window)
+        self.stride = (int(stride[0]), int(stride[1]))
+        self.cell = None if cell is None else (int(cell[0]), int(cell[1]))
+        self.fs = window_starts(self.F, self.window[0], self.stride[0])
+        self.book = LiveBook(self.window[1], self.stride[1], int(ring), None if cell is None else self.cell[1],
+                             table_indices)
+        self.names, self.ncls = _task_names(model, model_type)
+        K = sum(self.ncls)
+        if self.cell is not None:
+            from .ops.functional import window_cell_weights
+            if min(self.cell) < 1 or self.stride[1] > self.window[1]:
+                raise ValueError(f"a map needs a positive cell and windows that cover the recording: time stride "
+                                 f"at most {self.window[1]}")
+            self.wf = window_cell_weights(self.fs, self.window[0], self.F, self.cell[0])  # raises if rows uncovered
+        backend = _EngineLive if use_engine else _TorchLive
+        self.backend = backend(model, model_type, self.C, self.F, int(ring), self.fs, self.window, self.stride[1],
+                               self.book.jcap, K, batch, device)
+        self.backend.cf = self.cell[0] if self.cell is not None else None
+
+    @property
+    def total(self) -> int:
+        return self.book.total
+
+    @property
+    def captures(self) -> int:
+        """Graph captures so far (engine backend; 0 on the torch backend)."""
+        r = getattr(self.backend, "runner", None)
+        return r.captures if r is not None else 0
+
+    def _result(self, rows, starts, q_first: int, maps) -> Dict:
+        """``rows``: the new windows' table rows per step; ``maps``: the class maps of the steps' new columns."""
+        pos = np.asarray([(int(f0), t0) for _, t0 in starts for f0 in self.fs], dtype=np.int64).reshape(-1, 2)
+        rows = np.concatenate(rows) if rows else np.zeros((0, sum(self.ncls)), dtype=np.float32)
+        probs = [p.contiguous() for p in torch.from_numpy(rows).split(self.ncls, 1)]
+        res = _result(self.model_type, self.names, probs, pos, None)
+        if self.cell is not None:
+            maps = [m for m in maps if m is not None]
+            nfc = -(-self.F // self.cell[0])
+            m = np.concatenate(maps, 2) if maps else np.zeros((sum(self.ncls), nfc, 0))
+            # class_map: every class of the table, before the tasks are marginalised
+            res["map_columns"] = dict(_task_maps(m), first=q_first, last=self.book.q_done, class_map=m)
+        return res
+
+    def _emit(self, q0: int, q1: int, T: Optional[int]):
+        """The class map [K, nfc, q1 - q0] of the columns that became final."""
+        if q1 <= q0:
+            return None
+        cols = [live_time_weights(q, self.cell[1], self.window[1], self.stride[1], T) for q in range(q0, q1)]
+        return self.backend.map_columns(self.wf, cols)
+
+    @torch.no_grad()
+    def push(self, chunk) -> Dict:
+        if self.book.flushed:
+            raise RuntimeError("push after flush")
+        chunk = torch.as_tensor(chunk)
+        if chunk.dim() == 2:
+            chunk = chunk.unsqueeze(0)
+        if chunk.dim() != 3 or chunk.shape[0] != self.C or chunk.shape[1] != self.F or chunk.shape[2] < 1:
+            raise ValueError(f"a chunk must be [{self.C}, {self.F}, n >= 1], got {tuple(chunk.shape)}")
+        n = chunk.shape[2]
+        self.book.check_push(n)
+        rows, starts, maps, q_first, at = [], [], [], self.book.q_done, 0
+        for m in self.book.split(n):
+            (j0, j1), (q0, q1) = self.book.advance(m)
+            self.backend.append(chunk[:, :, at:at + m].float())
+            at += m
+            new = [(j, self.book.time_start(j)) for j in range(j0, j1)]
+            rows.append(self.backend.evaluate(new))
+            starts += new
+            if self.cell is not None:
+                maps.append(self._emit(q0, q1, None))
+        return self._result(rows, starts, q_first, maps)
+
+    @torch.no_grad()
+    def flush(self) -> Dict:
+        q_first = self.book.q_done
+        (j0, j1), (q0, q1) = self.book.finish()
+        self.backend.flush()
+        new = [(j, self.book.time_start(j)) for j in range(j0, j1)]
+        rows = [self.backend.evaluate(new)]
+        maps = [self._emit(q0, q1, self.book.total)] if self.cell is not None else []
+        return self._result(rows, new, q_first, maps)
+
+    def close(self):
+        """Release the backend (the engine's graph, ring and table)."""
+        if self.backend is not None:
+            self.backend.close()
+            self.backend = None

@@ -826,3 +826,133 @@ def window_map(probs: torch.Tensor, fs, ts, shape: Tuple[int, int], window: Tupl
                                 "ct": cell[1], "nfc": nfc, "ntc": ntc, "wf": ptr(wf), "wt": ptr(wt),
                                 "mf": wf.shape[1], "mt": wt.shape[1]}, fs_h, ts_h)
     return out
+
+
+# ---- live inference on a growing recording (csrc/live.hip) -----------------------------------------------------
+LIVE_TOTAL, LIVE_AVAIL, LIVE_NEXT, LIVE_JEND, LIVE_TEND, LIVE_NSTATE = range(6)
+
+
+def live_state(device) -> torch.Tensor:
+    """The device scalars of a live recording, int64 [LIVE_NSTATE]: total, avail, next = 0 and no end-aligned time
+    index (jend = -1)."""
+    s = torch.zeros(LIVE_NSTATE, dtype=torch.int64)
+    s[LIVE_JEND] = -1
+    return s.to(device)
+
+
+def _live_args(ring: torch.Tensor, state: torch.Tensor, nf: int, st: int, Wt: int) -> dict:
+    _check(ring, torch.float32)
+    _check(state, torch.int64)
+    if ring.dim() != 3:
+        raise ValueError("ring must be [C, F, R]")
+    if state.numel() != LIVE_NSTATE:
+        raise ValueError(f"state must hold {LIVE_NSTATE} int64 scalars (live_state)")
+    C, Fn, R = ring.shape
+    if R < Wt + 1:
+        raise ValueError(f"a ring of {R} time columns is below the window's {Wt} + 1")
+    if st < 1 or nf < 1:
+        raise ValueError("time stride and fiber window count must be positive")
+    return {"ring": ptr(ring), "state": ptr(state), "C": C, "F": Fn, "R": R, "nf": int(nf), "st": int(st),
+            "Wt": int(Wt)}
+
+
+def ring_append(ring: torch.Tensor, state: torch.Tensor, chunk: Optional[torch.Tensor], nf: int, st: int, Wt: int,
+                flush: bool = False) -> None:
+    """Append ``chunk`` [C, F, n] (fp32, ``n <= R - Wt``) to the time ring ``ring`` [C, F, R] -- sample ``t`` at
+    column ``t mod R`` -- and advance the device scalars ``state`` (:func:`live_state`): ``total += n`` and ``avail``,
+    the number of window numbers ``j * nf + a`` with ``j * st + Wt <= total``.  ``flush``: the stream ends at the new
+    total (``chunk`` may be None): if ``(total - Wt) mod st != 0`` the end-aligned time index becomes available."""
+    d = _live_args(ring, state, nf, st, Wt)
+    n = 0
+    if chunk is not None:
+        _check(chunk, torch.float32)
+        if chunk.dim() != 3 or tuple(chunk.shape[:2]) != tuple(ring.shape[:2]):
+            raise ValueError(f"chunk must be [{ring.shape[0]}, {ring.shape[1]}, n], got {tuple(chunk.shape)}")
+        n = chunk.shape[2]
+        if n > ring.shape[2] - Wt:
+            raise ValueError(f"a chunk of {n} samples overwrites data of a window not yet evaluated: at most "
+                             f"R - Wt = {ring.shape[2] - Wt}")
+    if n == 0 and not flush:
+        raise ValueError("an empty chunk")
+    d.update({"chunk": ptr(chunk) if n else 0, "n": n, "flush": int(flush)})
+    lib().ring_append(stream(), d)
+
+
+def gather_windows_ring(ring: torch.Tensor, state: torch.Tensor, fs, st: int, window: Tuple[int, int], B: int,
+                        taps: int = 0, off: int = 0, lab_w: int = 2):
+    """:func:`gather_windows` from the time ring: batch row ``r`` holds window ``next + r`` = ``(j, a)``, fiber start
+    ``fs[a]``, time start ``j * st`` (``tend`` for the end-aligned index), columns taken ``mod R``; rows from
+    ``avail`` on are zeros.  Returns (bf16 NHWC-8 batch, zero labels)."""
+    fs = _starts(fs, ring.device)
+    d = _live_args(ring, state, fs.numel(), st, window[1])
+    out = torch.empty(B, window[0], window[1], 8, device=ring.device, dtype=torch.bfloat16)
+    lab = torch.empty(B, lab_w, device=ring.device, dtype=torch.int64)
+    d.update({"fs": ptr(fs), "B": B, "Wf": window[0], "taps": taps, "off": off, "out": ptr(out), "lab_out": ptr(lab),
+              "lab_w": lab_w})
+    lib().gather_windows_ring(stream(), d)
+    return out, lab
+
+
+def live_probs(src: torch.Tensor, table: torch.Tensor, state: torch.Tensor, nf: int, jcap: int,
+               ncls: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """:func:`window_probs` for the live numbering: batch row ``r`` is window ``next + r`` = ``(j, a)`` and goes to
+    row ``(j mod jcap) * nf + a`` of the ring table ``table`` [>= jcap * nf, K] (in place); rows from ``avail`` on are
+    skipped.  The launch then advances ``next`` by the number of valid rows."""
+    _check(src, torch.float32)
+    _check(table, torch.float32)
+    _check(state, torch.int64)
+    if state.numel() != LIVE_NSTATE:
+        raise ValueError(f"state must hold {LIVE_NSTATE} int64 scalars (live_state)")
+    N, K = table.shape
+    if jcap < 1 or nf < 1 or N < jcap * nf:
+        raise ValueError(f"a table of {N} rows is below jcap * nf = {jcap * nf}")
+    if ncls is not None:
+        if src.dim() != 3 or src.shape[2] != 16 or src.shape[0] != len(ncls):
+            raise ValueError("log-probabilities must be [T, B, 16] with one ncls per task")
+        B = src.shape[1]
+    else:
+        if src.dim() != 2 or src.shape[1] != K:
+            raise ValueError("logits must be [B, K]")
+        B = src.shape[0]
+    d = {"state": ptr(state), "B": B, "nf": int(nf), "src": ptr(src), "softmax": int(ncls is None), "K": K,
+         "table": ptr(table), "nrows": N, "Jcap": int(jcap)}
+    if ncls is not None:
+        d["ncls"] = [int(k) for k in ncls]
+    lib().live_probs(stream(), d)
+    return table
+
+
+def live_map(table: torch.Tensor, fs, F: int, Wf: int, cf: int, jcap: int, jlo, wt) -> torch.Tensor:
+    """Cell columns of the map from the ring table ``table`` [>= jcap * len(fs), K] -> [K, ceil(F / cf), ncol]
+    (fp32).  Column ``q`` of the call is ``sum_a sum_j wf[a, i] wt[q][j] table[(j mod jcap) * nf + a]`` over the time
+    indices ``jlo[q] .. jlo[q] + len(wt[q]) - 1``: ``wt`` is a list of per-column fp64 weight vectors (the host's,
+    inference.live_time_weights), rounded to fp32 here; the fiber weights are :func:`window_map`'s bands."""
+    import numpy as np
+    _check(table, torch.float32)
+    fs_h = [int(v) for v in fs]
+    N, K = table.shape
+    ncol = len(jlo)
+    if ncol < 1 or len(wt) != ncol:
+        raise ValueError("one weight vector and one first time index per column")
+    jn = [len(w) for w in wt]
+    if min(jn) < 1 or max(jn) > jcap:
+        raise ValueError(f"a column needs 1 .. jcap = {jcap} time indices, got {min(jn)} .. {max(jn)}")
+    if N < jcap * len(fs_h):
+        raise ValueError(f"a table of {N} rows is below jcap * nf = {jcap * len(fs_h)}")
+    mw = max(jn)
+    band = np.zeros((ncol, mw), dtype=np.float32)
+    for q, w in enumerate(wt):
+        band[q, :len(w)] = np.asarray(w, dtype=np.float64).astype(np.float32)
+    dev = table.device
+    fs_d = _starts(fs_h, dev)
+    wf = _weight_band(window_cell_weights(fs_h, Wf, F, cf), fs_h, Wf, cf, dev)
+    wt_d = torch.from_numpy(band).to(dev)
+    jlo_d = torch.as_tensor([int(v) for v in jlo], dtype=torch.int64).to(dev)
+    jn_d = torch.as_tensor(jn, dtype=torch.int32).to(dev)
+    nfc = -(-F // cf)
+    out = torch.empty(K, nfc, ncol, device=dev, dtype=torch.float32)
+    lib().live_map(stream(), {"table": ptr(table), "fs": ptr(fs_d), "map": ptr(out), "wf": ptr(wf), "wt": ptr(wt_d),
+                              "jlo": ptr(jlo_d), "jn": ptr(jn_d), "mf": wf.shape[1], "mw": mw, "K": K, "F": F,
+                              "Wf": Wf, "cf": cf, "nfc": nfc, "Jcap": int(jcap), "nrows": N},
+                   fs_h, [int(v) for v in jlo], jn)
+    return out
