@@ -389,12 +389,27 @@ void noise_advance(int64_t draw, int64_t stream) {
   check(launch_noise_advance(reinterpret_cast<int64_t*>(static_cast<intptr_t>(draw)), S(stream)), "noise_advance");
 }
 
+// the batch geometry both inference paths' dicts carry
+WindowGeom parse_geom(const py::dict& d) {
+  WindowGeom g{};
+  g.fs = P<const int>(d, "fs"); g.C = (int)I(d, "C"); g.F = (int)I(d, "F"); g.nf = (int)I(d, "nf");
+  g.B = (int)I(d, "B"); g.Wf = (int)I(d, "Wf"); g.Wt = (int)I(d, "Wt");
+  g.taps = (int)I(d, "taps"); g.off = (int)I(d, "off");
+  return g;
+}
+
+// the tasks' class counts of a probability launch (absent: the softmax form)
+std::vector<int> parse_ncls(const py::dict& d, const char* what) {
+  std::vector<int> ncls;
+  if (d.contains("ncls")) ncls = d["ncls"].cast<std::vector<int>>();
+  if (ncls.size() > 4) throw std::runtime_error(std::string(what) + ": at most 4 tasks");
+  return ncls;
+}
+
 WindowArgs parse_window(const py::dict& d) {
   WindowArgs a{};
-  a.rec = P<const float>(d, "rec"); a.fs = P<const int>(d, "fs"); a.ts = P<const int>(d, "ts");
-  a.C = (int)I(d, "C"); a.F = (int)I(d, "F"); a.T = (int)I(d, "T"); a.nf = (int)I(d, "nf"); a.nt = (int)I(d, "nt");
-  a.B = (int)I(d, "B"); a.Wf = (int)I(d, "Wf"); a.Wt = (int)I(d, "Wt");
-  a.taps = (int)I(d, "taps"); a.off = (int)I(d, "off");
+  a.g = parse_geom(d);
+  a.rec = P<const float>(d, "rec"); a.ts = P<const int>(d, "ts"); a.T = (int)I(d, "T"); a.nt = (int)I(d, "nt");
   a.idx = P<const int64_t>(d, "idx"); a.cursor = P<int64_t>(d, "cursor");
   a.lo = I(d, "lo"); a.hi = I(d, "hi");
   return a;
@@ -406,9 +421,7 @@ void gather_windows(int64_t stream, py::dict d) {
 }
 
 void window_probs(int64_t stream, py::dict d) {
-  std::vector<int> ncls;
-  if (d.contains("ncls")) ncls = d["ncls"].cast<std::vector<int>>();
-  if (ncls.size() > 4) throw std::runtime_error("window_probs: at most 4 tasks");
+  const std::vector<int> ncls = parse_ncls(d, "window_probs");
   check(launch_window_probs(parse_window(d), P<const float>(d, "src"), (int)I(d, "softmax"), (int)ncls.size(),
                             ncls.data(), (int)I(d, "K"), P<float>(d, "probs"), I(d, "nprobs"), S(stream)),
         "window_probs");
@@ -427,10 +440,8 @@ void window_map(int64_t stream, py::dict d, std::vector<int> fs, std::vector<int
 
 LiveArgs parse_live(const py::dict& d) {
   LiveArgs a{};
-  a.ring = P<float>(d, "ring"); a.fs = P<const int>(d, "fs"); a.state = P<int64_t>(d, "state");
-  a.C = (int)I(d, "C"); a.F = (int)I(d, "F"); a.R = (int)I(d, "R"); a.nf = (int)I(d, "nf"); a.st = (int)I(d, "st");
-  a.B = (int)I(d, "B"); a.Wf = (int)I(d, "Wf"); a.Wt = (int)I(d, "Wt");
-  a.taps = (int)I(d, "taps"); a.off = (int)I(d, "off");
+  a.g = parse_geom(d);
+  a.ring = P<float>(d, "ring"); a.state = P<int64_t>(d, "state"); a.R = (int)I(d, "R"); a.st = (int)I(d, "st");
   return a;
 }
 
@@ -445,9 +456,7 @@ void gather_windows_ring(int64_t stream, py::dict d) {
 }
 
 void live_probs(int64_t stream, py::dict d) {
-  std::vector<int> ncls;
-  if (d.contains("ncls")) ncls = d["ncls"].cast<std::vector<int>>();
-  if (ncls.size() > 4) throw std::runtime_error("live_probs: at most 4 tasks");
+  const std::vector<int> ncls = parse_ncls(d, "live_probs");
   check(launch_live_probs(parse_live(d), P<const float>(d, "src"), (int)I(d, "softmax"), (int)ncls.size(),
                           ncls.data(), (int)I(d, "K"), P<float>(d, "table"), I(d, "nrows"), (int)I(d, "Jcap"),
                           S(stream)), "live_probs");

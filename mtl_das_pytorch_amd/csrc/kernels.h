@@ -336,15 +336,22 @@ int launch_gather_batch_noise(const float* X, const int64_t* idx, const int64_t*
                               hipStream_t st);
 int launch_noise_advance(int64_t* draw, hipStream_t st);
 int launch_pool3(int is_max, int backward, const PoolArgs& a, hipStream_t st);
-// window.hip: resident-recording inference -- windows cut on the device, probabilities into a resident table,
-// overlapping windows averaged into a cell map
-struct WindowArgs {
-  const float* rec;   // recording [C][F][T] fp32 (gather_windows only)
-  const int* fs;      // window starts along the fiber [nf] and along time [nt]; window n = a * nt + b
-  const int* ts;
-  int C, F, T, nf, nt;
+// window.hip / live.hip: sliding-window inference over a resident and over a growing recording.  What the two share
+// -- the batch geometry below, the gather body, the probability element, the fiber side of the maps and the
+// launchers' common checks -- is in window_batch.h.
+struct WindowGeom {
+  const int* fs;      // window starts along the fiber [nf]
+  int C, F, nf;       // channels and fiber rows of the source, fiber window count
   int B, Wf, Wt;      // batch rows, window size
   int taps, off;      // vertical tap packing of a 1-channel stem (gather_batch)
+};
+// window.hip: windows cut on the device from a recording [C][F][T], probabilities into a resident table,
+// overlapping windows averaged into a cell map
+struct WindowArgs {
+  WindowGeom g;
+  const float* rec;   // recording [C][F][T] fp32 (gather_windows only)
+  const int* ts;      // window starts along time [nt]; window n = a * nt + b
+  int T, nt;
   // batch row r holds window idx[r], or lo + *cursor * B + r (exactly one of idx / cursor is set); a row whose
   // window number is outside [lo, hi) is padding: gathered as zeros, skipped by window_probs
   const int64_t* idx;
@@ -360,7 +367,7 @@ struct MapArgs {
   const int* fs;       // device copies of the start tables
   const int* ts;
   float* map;          // [K][nfc][ntc]
-  // per-axis weights of a window in the cells it reaches, as bands (window.hip window_map_kernel): wf [nf][mf] from
+  // per-axis weights of a window in the cells it reaches, as bands (window_batch.h band_weight): wf [nf][mf] from
   // cell row fs[a] / cf on, wt [nt][mt] from cell column ts[b] / ct on; mf = (Wf - 1) / cf + 2, mt likewise
   const float* wf;
   const float* wt;
@@ -373,15 +380,13 @@ int launch_window_map(const MapArgs& a, const int* h_fs, const int* h_ts, hipStr
 // (n = j * nf + a: time index j starts at j * st), probabilities into a ring table, final map columns
 enum { LIVE_TOTAL = 0, LIVE_AVAIL, LIVE_NEXT, LIVE_JEND, LIVE_TEND, LIVE_NSTATE };
 struct LiveArgs {
+  WindowGeom g;
   float* ring;        // [C][F][R] fp32: time sample t at column t mod R
-  const int* fs;      // window starts along the fiber [nf]
   // device scalars [LIVE_NSTATE]: total = time samples received; avail = window numbers that can be evaluated;
   // next = the first window number not evaluated yet (batch row r holds window next + r, padding from avail on);
   // jend / tend = number and start of the end-aligned time index (jend = -1 until the stream is flushed)
   int64_t* state;
-  int C, F, R, nf, st;
-  int B, Wf, Wt;      // batch rows, window size
-  int taps, off;      // vertical tap packing of a 1-channel stem (gather_batch)
+  int R, st;
 };
 // chunk [C][F][n] (n <= R - Wt) -> ring, total += n, avail from the new total; flush: the stream ends at the new
 // total (n may be 0) and the end-aligned index, if there is one, becomes available.  -2 on bad arguments, as below.

@@ -1,0 +1,152 @@
+// Pieces shared by the two sliding-window inference paths: the resident recording (window.hip) and the growing
+// recording whose time axis is a ring (live.hip).  One copy of
+//
+//   * the gather body: the NHWC-8 pixel loop with the stem's tap packing and the window-edge padding, a template
+//     over the source (where batch row b's window starts, which column holds time t, base pointer and row pitch);
+//   * the probability element: softmax of a logits row, or exp of the owning task's log-probability;
+//   * the fiber side of the maps: the windows covering a cell (bisection) and the weight-band lookup;
+//   * the launchers' common checks: the batch geometry, the ncls packing, "the starts cover the axis".
+//
+// What differs stays in the kernels: how a batch row is numbered and where its probabilities go, the counter
+// advance, and the maps' time loops (bands over ts in window.hip, per-column weight vectors over the ring table in
+// live.hip).  The maps' sums `acc += (wf * wt) * p` are written out in each kernel: their rounding is the kernel's.
+#pragma once
+#include "kernels.h"
+
+namespace mda {
+
+// One thread per output pixel, threads along t (the source's contiguous axis).  The padding of the tap packing is
+// the window's: channel j of pixel (h, w) is x[h - off + j][w] inside the window, zero outside it even where the
+// source has rows there.  A batch row that is no window (src.window false: padding, or a start outside the source)
+// is written as zeros and reads nothing.  Source:
+//   bool window(int b, int& f0, T& t0)   batch row b is a window, starting at fiber row f0 and time t0
+//   int64_t column(t)                    the column of the source that holds time t
+//   const float* base(); int64_t pitch() the source is [C][F][pitch] fp32
+template <class Source>
+DEV void gather_windows_body(const WindowGeom& g, const Source& src, bf16_t* __restrict__ out,
+                             int64_t* __restrict__ lab_out, int lab_w) {
+  const int HW = g.Wf * g.Wt;
+  const int64_t M = (int64_t)g.B * HW;
+  const float* __restrict__ x = src.base();
+  const int64_t pitch = src.pitch(), plane = (int64_t)g.F * pitch;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < M; p += (int64_t)gridDim.x * 256) {
+    const int b = (int)p / HW;  // M < 2^31 (gather_geom_ok)
+    const int r = (int)p - b * HW;
+    const int h = r / g.Wt, w = r - h * g.Wt;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = 0.f;
+    int f0;
+    typename Source::time_type t0;
+    if (src.window(b, f0, t0) && f0 >= 0 && f0 + g.Wf <= g.F) {
+      const int64_t col = src.column(t0 + w);
+      if (g.taps > 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int hh = h - g.off + j;
+          if (j < g.taps && hh >= 0 && hh < g.Wf) v[j] = x[(int64_t)(f0 + hh) * pitch + col];
+        }
+      } else {
+        const int64_t at = (int64_t)(f0 + h) * pitch + col;
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+          if (c < g.C) v[c] = x[c * plane + at];
+      }
+    }
+    store8(out + p * 8, v);
+  }
+  // the head kernels read labels for their metrics: inference has none
+  if (blockIdx.x == 0)
+    for (int i = threadIdx.x; i < g.B * lab_w; i += 256) lab_out[i] = 0;
+}
+
+// What both gather launchers require of the geometry and the outputs.
+inline bool gather_geom_ok(const WindowGeom& g, const bf16_t* out, const int64_t* lab_out, int lab_w) {
+  return g.fs && out && lab_out && lab_w >= 0 && g.B >= 1 && g.nf >= 1 && g.C >= 1 && g.C <= 8 && g.taps >= 0 &&
+         g.taps <= 8 && !(g.taps > 0 && g.C != 1) && g.Wf >= 1 && g.Wt >= 1 && g.Wf <= g.F &&
+         (int64_t)g.B * g.Wf * g.Wt < (1ll << 31);
+}
+
+template <class Kernel, class Args>
+int launch_gather(Kernel kernel, const Args& a, bf16_t* out, int64_t* lab_out, int lab_w, hipStream_t st) {
+  const int64_t M = (int64_t)a.g.B * a.g.Wf * a.g.Wt;
+  const int blocks = (int)std::min<int64_t>((M + 255) / 256, 65535);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, a, out, lab_out, lab_w);
+  return (int)hipGetLastError();
+}
+
+// Column c of batch row r of the probability table.  softmax = 0 (Models A/B): src is logp [T][B][16] and the
+// column is exp(logp[t][r][c - c0_t]) of the task t that owns it (nc[t] columns each, side by side).  softmax = 1
+// (Model C): src is logits [B][K] and the row is their max-subtracted softmax; every thread of a row recomputes its
+// max and sum (2 K expf) in the same order.
+DEV float window_prob(const float* __restrict__ src, int softmax, int T, const int (&nc)[4], int K, int B, int r,
+                      int c) {
+  if (softmax) {
+    const float* x = src + (int64_t)r * K;
+    float mx = x[0];
+    for (int k = 1; k < K; ++k) mx = fmaxf(mx, x[k]);
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s += expf(x[k] - mx);
+    return expf(x[c] - mx) / s;
+  }
+  int t = 0, c0 = 0;
+  while (t + 1 < T && c >= c0 + nc[t]) c0 += nc[t++];
+  return expf(src[((int64_t)t * B + r) * 16 + (c - c0)]);
+}
+
+// The class counts of the T <= 4 tasks as the probability kernels take them; false unless every count is in
+// 1 .. 16 and they sum to K.  The softmax form has no tasks and packs zeros.
+inline bool pack_ncls(int softmax, int T, const int* ncls, int K, int4& nc) {
+  int sum = 0, v[4] = {0, 0, 0, 0};
+  if (!softmax) {
+    if (T < 1 || T > 4 || !ncls) return false;
+    for (int t = 0; t < T; ++t) {
+      if (ncls[t] < 1 || ncls[t] > 16) return false;
+      v[t] = ncls[t];
+      sum += ncls[t];
+    }
+    if (sum != K) return false;
+  }
+  nc = make_int4(v[0], v[1], v[2], v[3]);
+  return true;
+}
+
+// The windows overlapping [r0, r1) of one axis: starts are strictly increasing, so they are the contiguous
+// range first(s + win > r0) .. last(s < r1), found by bisection.
+DEV void covering_range(const int* __restrict__ s, int n, int win, int r0, int r1, int& a0, int& a1) {
+  int lo = 0, hi = n;  // first index with s[i] > r0 - win
+  while (lo < hi) {
+    const int m = (lo + hi) >> 1;
+    if (s[m] > r0 - win) hi = m; else lo = m + 1;
+  }
+  a0 = lo;
+  hi = n;  // first index with s[i] >= r1
+  while (lo < hi) {
+    const int m = (lo + hi) >> 1;
+    if (s[m] >= r1) hi = m; else lo = m + 1;
+  }
+  a1 = lo;  // exclusive
+}
+
+// The weight of window a in cell i of its axis.  The host computes a window's weights in fp64 and passes them as
+// bands: window a reaches at most m = (win - 1) / cell + 2 cells from s[a] / cell on, and its weights for them are
+// band[a * m ..].  False outside the band (a covering window's cell is inside it).
+DEV bool band_weight(const int* __restrict__ s, const float* __restrict__ band, int m, int cell, int a, int i,
+                     float& w) {
+  const int d = i - s[a] / cell;
+  if (d < 0 || d >= m) return false;
+  w = band[(int64_t)a * m + d];
+  return true;
+}
+
+// every sample of [0, len) is inside a window: starts strictly increasing, first at 0, no gap, last reaches len
+inline bool starts_cover(const int* s, int n, int win, int len) {
+  if (n < 1 || win < 1 || s[0] != 0 || s[n - 1] + (int64_t)win < len) return false;
+  for (int i = 0; i < n; ++i) {
+    if (s[i] < 0 || s[i] + (int64_t)win > len) return false;
+    if (i && (s[i] <= s[i - 1] || s[i] > s[i - 1] + (int64_t)win)) return false;
+  }
+  return true;
+}
+
+}  // namespace mda

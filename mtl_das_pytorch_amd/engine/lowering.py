@@ -8,7 +8,7 @@ from typing import Callable, Dict, List, Optional
 
 import torch
 
-from ..ops.functional import WGRAD_PATCH, WGRAD_TILES, noise_args, wgrad_ktiles
+from ..ops.functional import LIVE_NSTATE, WGRAD_PATCH, WGRAD_TILES, noise_args, wgrad_ktiles
 from ..ops.hip import lib
 from .core import (GRAD_DT, Act, BNLayer, ConvLayer, P, build_optseg_table, build_wgfin_table, optimizer_segments,
                    pad_to)
@@ -441,23 +441,39 @@ class LoweredProgram:
             raise ValueError(f"idx must hold {self.B} window numbers")
         return {"B": self.B, "idx": P(idx), "cursor": P(cursor), "lo": int(lo), "hi": int(hi)}
 
+    def _window_source(self, x, what: str):
+        """``x``: the recording [C, F, T] or the time ring [C, F, R] of an inference gather."""
+        if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+            raise ValueError(f"the {what} must be a contiguous fp32 3-d tensor on the device")
+        if self.stem_pack[0] and x.shape[0] != 1:
+            raise ValueError("stem tap packing needs a single-channel input")
+
+    @staticmethod
+    def _device_vector(t, dtype, what: str, numel: Optional[int] = None):
+        if (t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or not t.is_cuda
+                or (numel is not None and t.numel() != numel)):
+            raise ValueError(f"{what} must be a contiguous {str(dtype)[6:]} device vector"
+                             + (f" of {numel}" if numel is not None else ""))
+
+    def _stem_fields(self, x, fs) -> dict:
+        """What a window gather writes -- the stem's input and the labels -- and the geometry it shares with the
+        source ``x`` [C, F, .] and the fiber start table."""
+        return {"C": x.shape[0], "F": x.shape[1], "fs": P(fs), "nf": fs.numel(), "B": self.B, "Wf": self.H0,
+                "Wt": self.W0, "taps": self.stem_pack[0], "off": self.stem_pack[1], "out": P(self.x),
+                "lab_out": P(self.labels), "lab_w": self.label_width}
+
     def window_gather_phase(self, rec, fs, ts, idx=None, cursor=None, lo: int = 0, hi: Optional[int] = None) -> Phase:
         """The batch gather of resident-recording inference: the batch's (H0, W0) windows are cut from ``rec``
         ([C, F, T] fp32 on the device) into the stem's input, labels zeroed.  ``fs`` / ``ts``: int32 device
         tables of the window starts, window ``n = a * len(ts) + b``; batch row ``r`` is window ``idx[r]`` or
         ``lo + cursor * B + r`` (``cursor``: a device int64 scalar that window_probs_phase advances); rows whose
         window number is outside ``[lo, hi)`` are zeros."""
-        if rec.dim() != 3 or rec.dtype != torch.float32 or not rec.is_contiguous() or not rec.is_cuda:
-            raise ValueError("recording must be a contiguous fp32 [C, F, T] tensor on the device")
-        if self.stem_pack[0] and rec.shape[0] != 1:
-            raise ValueError("stem tap packing needs a single-channel input")
+        self._window_source(rec, "recording")
         for t in (fs, ts):
-            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or not t.is_cuda:
-                raise ValueError("window-start tables must be contiguous int32 vectors on the device")
+            self._device_vector(t, torch.int32, "a window-start table")
         d = self._window_args(idx, cursor, lo, fs.numel() * ts.numel() if hi is None else hi)
-        d.update({"rec": P(rec), "fs": P(fs), "ts": P(ts), "C": rec.shape[0], "F": rec.shape[1], "T": rec.shape[2],
-                  "nf": fs.numel(), "nt": ts.numel(), "Wf": self.H0, "Wt": self.W0, "taps": self.stem_pack[0],
-                  "off": self.stem_pack[1], "out": P(self.x), "lab_out": P(self.labels), "lab_w": self.label_width})
+        d.update(self._stem_fields(rec, fs))
+        d.update({"rec": P(rec), "ts": P(ts), "T": rec.shape[2], "nt": ts.numel()})
         ph = Phase("window_gather")
         ph.add("gather_windows", k_gather_windows, d)
         ph.keep = (rec, fs, ts, idx, cursor)  # the launch holds their device pointers
@@ -470,29 +486,30 @@ class LoweredProgram:
             return [self.logp.shape[1]]
         return [16 if o == 0 else 2 for o in self.lab_off]
 
+    def _prob_fields(self, table) -> dict:
+        """The source side of a probability launch -- the heads' log-probabilities or Model C's logits, for the
+        columns of :meth:`prob_classes` -- after checking that ``table`` has those columns."""
+        ncls = self.prob_classes()
+        if (table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous() or not table.is_cuda
+                or table.shape[1] != sum(ncls)):
+            raise ValueError(f"probability table must be a contiguous fp32 [N, {sum(ncls)}] tensor on the device")
+        softmax = self.logp.dim() == 2
+        d = {"B": self.B, "src": P(self.logp), "softmax": int(softmax), "K": table.shape[1]}
+        if not softmax:
+            d["ncls"] = ncls
+        return d
+
     def window_probs_phase(self, probs, idx=None, cursor=None, lo: int = 0, hi: Optional[int] = None) -> Phase:
         """After ``fwd_eval``: the batch's probabilities into rows of the resident table ``probs`` [N, K] (fp32) --
         ``exp`` of the heads' log-probabilities, or the softmax of Model C's logits -- for the batch rows whose
         window number is in ``[lo, hi)``; in cursor form the launch then advances the cursor by one."""
-        ncls = self.prob_classes()
-        if (probs.dtype != torch.float32 or probs.dim() != 2 or not probs.is_contiguous() or not probs.is_cuda
-                or probs.shape[1] != sum(ncls)):
-            raise ValueError(f"probability table must be a contiguous fp32 [N, {sum(ncls)}] tensor on the device")
-        d = self._window_args(idx, cursor, lo, probs.shape[0] if hi is None else hi)
-        softmax = self.logp.dim() == 2
-        d.update({"src": P(self.logp), "softmax": int(softmax), "K": probs.shape[1], "probs": P(probs),
-                  "nprobs": probs.shape[0]})
-        if not softmax:
-            d["ncls"] = ncls
+        d = self._prob_fields(probs)
+        d.update(self._window_args(idx, cursor, lo, probs.shape[0] if hi is None else hi))
+        d.update({"probs": P(probs), "nprobs": probs.shape[0]})
         ph = Phase("window_probs")
         ph.add("window_probs", k_window_probs, d)
         ph.keep = (probs, idx, cursor)
         return ph
-
-    @staticmethod
-    def _live_state_ok(state):
-        if state.dtype != torch.int64 or not state.is_cuda or not state.is_contiguous() or state.numel() != 5:
-            raise ValueError("the live scalars must be a contiguous int64 [5] tensor on the device (live_state)")
 
     def live_gather_phase(self, ring, fs, state, st: int) -> Phase:
         """The batch gather of live inference: the batch's (H0, W0) windows are cut from the time ring ``ring``
@@ -500,19 +517,13 @@ class LoweredProgram:
         ``r`` is window ``next + r`` = ``(j, a)`` -- fiber start ``fs[a]`` (int32 device table), time start
         ``j * st`` -- while that is below ``avail``; the other rows are zeros (``state``: the device scalars of
         ops.functional.live_state, advanced by ring_append and live_probs_phase)."""
-        if ring.dim() != 3 or ring.dtype != torch.float32 or not ring.is_contiguous() or not ring.is_cuda:
-            raise ValueError("ring must be a contiguous fp32 [C, F, R] tensor on the device")
-        if self.stem_pack[0] and ring.shape[0] != 1:
-            raise ValueError("stem tap packing needs a single-channel input")
-        if fs.dtype != torch.int32 or fs.dim() != 1 or not fs.is_contiguous() or not fs.is_cuda:
-            raise ValueError("the fiber window-start table must be a contiguous int32 vector on the device")
+        self._window_source(ring, "ring")
+        self._device_vector(fs, torch.int32, "the fiber window-start table")
         if ring.shape[2] < self.W0 + 1:
             raise ValueError(f"a ring of {ring.shape[2]} time columns is below the window's {self.W0} + 1")
-        self._live_state_ok(state)
-        d = {"ring": P(ring), "fs": P(fs), "state": P(state), "C": ring.shape[0], "F": ring.shape[1],
-             "R": ring.shape[2], "nf": fs.numel(), "st": int(st), "B": self.B, "Wf": self.H0, "Wt": self.W0,
-             "taps": self.stem_pack[0], "off": self.stem_pack[1], "out": P(self.x), "lab_out": P(self.labels),
-             "lab_w": self.label_width}
+        self._device_vector(state, torch.int64, "the live scalars (live_state)", LIVE_NSTATE)
+        d = self._stem_fields(ring, fs)
+        d.update({"ring": P(ring), "state": P(state), "R": ring.shape[2], "st": int(st)})
         ph = Phase("live_gather")
         ph.add("gather_windows_ring", k_gather_windows_ring, d)
         ph.keep = (ring, fs, state)  # the launch holds their device pointers
@@ -521,18 +532,11 @@ class LoweredProgram:
     def live_probs_phase(self, table, state, nf: int, jcap: int) -> Phase:
         """After ``fwd_eval``: the valid batch rows' probabilities into the ring table ``table`` [>= jcap * nf, K]
         at row ``(j mod jcap) * nf + a``; the launch then advances ``next`` by the number of valid rows."""
-        ncls = self.prob_classes()
-        if (table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous() or not table.is_cuda
-                or table.shape[1] != sum(ncls)):
-            raise ValueError(f"probability table must be a contiguous fp32 [N, {sum(ncls)}] tensor on the device")
+        d = self._prob_fields(table)
         if jcap < 1 or nf < 1 or table.shape[0] < jcap * nf:
             raise ValueError(f"a table of {table.shape[0]} rows is below jcap * nf = {jcap * nf}")
-        self._live_state_ok(state)
-        softmax = self.logp.dim() == 2
-        d = {"state": P(state), "B": self.B, "nf": int(nf), "src": P(self.logp), "softmax": int(softmax),
-             "K": table.shape[1], "table": P(table), "nrows": table.shape[0], "Jcap": int(jcap)}
-        if not softmax:
-            d["ncls"] = ncls
+        self._device_vector(state, torch.int64, "the live scalars (live_state)", LIVE_NSTATE)
+        d.update({"state": P(state), "nf": int(nf), "table": P(table), "nrows": table.shape[0], "Jcap": int(jcap)})
         ph = Phase("live_probs")
         ph.add("live_probs", k_live_probs, d)
         ph.keep = (table, state)

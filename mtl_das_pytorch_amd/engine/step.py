@@ -39,7 +39,8 @@ every push of the stream; ``captures`` counts the captures of a runner.
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, List, Optional
+import dataclasses
+from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
@@ -69,6 +70,32 @@ def capture_graph(fns, error_mode: str = "global"):
         for f in fns:
             f()
     return g, keeper
+
+
+@dataclasses.dataclass
+class InferSource:
+    """What a runner's inference graph (kind "infer" or "live") was built from.  Another tensor or another constant
+    is another graph: the launches hold the device pointers and the constants."""
+    tensors: Dict[str, torch.Tensor]  # by name; compared by identity
+    consts: Dict[str, int]            # compared by value
+    rollback: Tuple[str, ...]         # the tensors the step writes: a warm-up may not leave them changed
+    phases: Callable                  # (program, source) -> (gather phase, store phase) around fwd_eval
+    key: object = None                # what the source's owner knows it by (inference.resident_probs)
+
+    def same(self, o: "InferSource") -> bool:
+        return all(t is o.tensors[k] for k, t in self.tensors.items()) and self.consts == o.consts
+
+
+def _window_phases(p, s: InferSource):
+    t = s.tensors
+    return (p.window_gather_phase(t["rec"], t["fs"], t["ts"], cursor=t["cursor"], **s.consts),
+            p.window_probs_phase(t["probs"], cursor=t["cursor"], **s.consts))
+
+
+def _live_phases(p, s: InferSource):
+    t, c = s.tensors, s.consts
+    return (p.live_gather_phase(t["ring"], t["fs"], t["state"], c["st"]),
+            p.live_probs_phase(t["table"], t["state"], t["fs"].numel(), c["jcap"]))
 
 
 class StepRunner:
@@ -113,10 +140,9 @@ class StepRunner:
         self.buckets = list(program.buckets or [(0, program.flat.numel)])
         self.schedule = None  # [nrows][B] batch-index schedule (set_index_schedule)
         self.cursor = None
-        self.window = None  # resident-recording inference (set_window_source): (rec, fs, ts, probs, lo, hi)
+        # inference sources by graph kind: "infer" (set_window_source) and "live" (set_live_source)
+        self.inference: Dict[str, InferSource] = {}
         self.window_cursor = None
-        self.window_key = None  # what the source's owner knows it by (inference.resident_probs: shape and starts)
-        self.live = None  # live inference (set_live_source): (ring, fs, state, table, st, jcap)
         self.captures = 0  # graphs captured so far (a live source is captured once, whatever is pushed)
         # SNR noise in the gather (set_train_noise / set_eval_noise): per mode the launch constant (seed; None: off)
         # and the device scalars the captured graphs read -- fp32 (lo, hi) and the int64 draw number
@@ -204,11 +230,10 @@ class StepRunner:
 
     def _mutable_state(self, kind: Optional[str] = None) -> List[torch.Tensor]:
         f = self.p.flat
-        # the inference step advances its batch cursor and fills rows of the probability table: a warm-up that
-        # left either behind would skip the first batch
-        infer = [self.window_cursor, self.window[3]] if kind == "infer" else []
-        if kind == "live":  # next / avail / total and the table: a warm-up may not consume windows
-            infer = [self.live[2], self.live[3]]
+        # an inference step advances its batch cursor (live: next) and fills rows of the probability table: a
+        # warm-up that left either behind would skip the first batch
+        src = self.inference.get(kind)
+        infer = [src.tensors[k] for k in src.rollback] if src is not None else []
         return ([f.params, f.grads, f.exp_avg, f.exp_avg_sq, f.bn_mean, f.bn_var, f.bn_nbt, f.step, self.p.metrics,
                  self.p.confusion, self.p.logp] + list(self.p.extra_state)
                 + ([self.cursor] if self.cursor is not None else []) + infer
@@ -222,15 +247,8 @@ class StepRunner:
 
     def _phases(self, kind: str) -> List[Callable[[], None]]:
         p = self.p
-        if kind == "infer":
-            rec, fs, ts, probs, lo, hi = self.window
-            gather = p.window_gather_phase(rec, fs, ts, cursor=self.window_cursor, lo=lo, hi=hi)
-            store = p.window_probs_phase(probs, cursor=self.window_cursor, lo=lo, hi=hi)
-            return [gather.run, p.fwd_eval.run, store.run]
-        if kind == "live":
-            ring, fs, state, table, st, jcap = self.live
-            gather = p.live_gather_phase(ring, fs, state, st)
-            store = p.live_probs_phase(table, state, fs.numel(), jcap)
+        if kind in self.inference:
+            gather, store = self.inference[kind].phases(p, self.inference[kind])
             return [gather.run, p.fwd_eval.run, store.run]
         X, lab = self.sources["train" if kind.startswith("train") else "eval"]
         # a training step's gather also zeroes the arena's accumulators (one launch; arena.clear otherwise)
@@ -365,7 +383,7 @@ class StepRunner:
         ``n = a * len(ts) + b``) -- and writes their probabilities into rows of ``probs`` [N, K]; the step's last
         kernel advances the batch cursor, so ceil((hi - lo) / B) calls cover the range with no host copy between
         them.  The cursor restarts at ``lo``.  Other tensors or another range rebuild the captured graph (its
-        launches hold the device pointers and the range).  ``key``: kept as ``window_key`` until the source is
+        launches hold the device pointers and the range).  ``key``: kept as the source's ``key`` until it is
         replaced or cleared -- how a caller that uploaded the tensors recognises them again."""
         hi = fs.numel() * ts.numel() if hi is None else hi
         if probs.shape[0] != fs.numel() * ts.numel():
@@ -374,25 +392,18 @@ class StepRunner:
             raise ValueError(f"window range [{lo}, {hi}) outside the {probs.shape[0]} windows")
         if self.window_cursor is None:
             self.window_cursor = torch.zeros(1, dtype=torch.int64, device=self.p.device)
-        cur = self.window
-        new = (rec, fs, ts, probs, int(lo), int(hi))
-        if cur is None or any(a is not b for a, b in zip(cur[:4], new[:4])) or cur[4:] != new[4:]:
-            self.window = new
-            self._drop_graph("infer")
-        self.window_key = key
+        self._set_source("infer", InferSource({"rec": rec, "fs": fs, "ts": ts, "probs": probs,
+                                               "cursor": self.window_cursor}, {"lo": int(lo), "hi": int(hi)},
+                                              ("cursor", "probs"), _window_phases)).key = key
         self.window_cursor.zero_()
 
     def clear_window_source(self):
         """Release the window source (the recording and its table can be freed before the next one is uploaded)."""
-        self._drop_graph("infer")
-        self.window = self.window_key = None
+        self._clear_source("infer")
 
     def infer_step(self):
         """One batch of the window source: [window gather, eval forward, probabilities + cursor], one graph."""
-        if self.window is None:
-            raise ValueError("infer_step() needs set_window_source")
-        if not self._packed:
-            self.pack_weights()
+        self._source_ready("infer", "infer_step() needs set_window_source")
         self._run("infer")
 
     def set_live_source(self, ring: torch.Tensor, fs: torch.Tensor, state: torch.Tensor, table: torch.Tensor,
@@ -403,33 +414,41 @@ class StepRunner:
         kernel advances ``next`` by the valid rows.  ``state``: the device scalars (ops.functional.live_state) that
         ring_append advances as data arrives.  The graph is captured once per source: pushes, the wrap of the ring
         and the end of the stream only change device state."""
-        new = (ring, fs, state, table, int(st), int(jcap))
-        cur = self.live
-        if cur is None or any(a is not b for a, b in zip(cur[:4], new[:4])) or cur[4:] != new[4:]:
-            self.live = new
-            self._drop_graph("live")
+        self._set_source("live", InferSource({"ring": ring, "fs": fs, "state": state, "table": table},
+                                             {"st": int(st), "jcap": int(jcap)}, ("state", "table"), _live_phases))
 
     def clear_live_source(self):
         """Release the live source (its graph, and the runner's hold on the ring and the table)."""
-        self._drop_graph("live")
-        self.live = None
+        self._clear_source("live")
 
     def prepare_live(self):
         """Capture the live graph now (side effects rolled back), so that no push pays for it."""
-        if self.live is None:
-            raise ValueError("prepare_live() needs set_live_source")
-        if not self._packed:
-            self.pack_weights()
+        self._source_ready("live", "prepare_live() needs set_live_source")
         if self.use_graph:
             self._ensure_graph("live")
 
     def live_step(self):
         """One batch of the live source: [ring gather, eval forward, probabilities + next], one graph."""
-        if self.live is None:
-            raise ValueError("live_step() needs set_live_source")
+        self._source_ready("live", "live_step() needs set_live_source")
+        self._run("live")
+
+    def _set_source(self, kind: str, new: InferSource) -> InferSource:
+        """Bind an inference source; the kind's graph survives only if it was built from the same one."""
+        cur = self.inference.get(kind)
+        if cur is None or not cur.same(new):
+            self._drop_graph(kind)
+            self.inference[kind] = cur = new
+        return cur
+
+    def _clear_source(self, kind: str):
+        self._drop_graph(kind)
+        self.inference.pop(kind, None)
+
+    def _source_ready(self, kind: str, unbound: str):
+        if kind not in self.inference:
+            raise ValueError(unbound)
         if not self._packed:
             self.pack_weights()
-        self._run("live")
 
     def reset_metrics(self):
         self.p.metrics.zero_()

@@ -95,9 +95,7 @@ def predict_recording(model: nn.Module, model_type: str, rec: torch.Tensor, stri
         raise ValueError("windows='resident' needs the engine backend")
     if runner is not None and windows != "resident":
         raise ValueError("a window runner serves windows='resident' only")
-    names = {"MTL": ["distance", "event"], "single_distance": ["distance"], "single_event": ["event"],
-             "multi_classifier": ["joint"]}[model_type]
-    ncls = {"distance": 16, "event": 2, "joint": model.num_classes if model_type == "multi_classifier" else 0}
+    names, ncls = _task_names(model, model_type)
     if windows == "resident":
         rec3 = rec.float().unsqueeze(0) if rec.dim() == 2 else rec.float()
         fs, ts = window_starts(rec3.shape[1], WINDOW[0], stride[0]), window_starts(rec3.shape[2], WINDOW[1], stride[1])
@@ -108,13 +106,13 @@ def predict_recording(model: nn.Module, model_type: str, rec: torch.Tensor, stri
             table = resident_probs(runner, rec3, fs, ts, lo, hi)
         else:
             table = _resident_probs(model, model_type, rec3, fs, ts, lo, hi, batch, device)
-        probs = [p.contiguous() for p in table.split([ncls[t] for t in names], 1)]
+        probs = [p.contiguous() for p in table.split(ncls, 1)]
         return _result(model_type, names, probs, pos, ctx)
     tiles, pos = sliding_windows(rec.float(), stride=stride)
     n = len(tiles)
     lo, hi = _shard(n, ctx)
     mine = tiles[lo:hi].to(device)
-    probs = [torch.zeros(n, ncls[t], device=device) for t in names]
+    probs = [torch.zeros(n, k, device=device) for k in ncls]
     if len(mine):
         if use_engine:
             chunks = _engine_probs(model, model_type, mine, batch, device)
@@ -152,16 +150,8 @@ def _engine_probs(model: nn.Module, model_type: str, x: torch.Tensor, batch: int
     """Eval-mode forward of the lowered program over window batches (the last batch padded)."""
     from .engine.step import StepRunner
     n = len(x)
-    if model_type == "multi_classifier":
-        from .engine.inception import InceptionProgram
-        prog = InceptionProgram(model, batch, device, in_hw=tuple(x.shape[2:]), p_drop=0.0)
-        labels = torch.zeros(n, dtype=torch.int64, device=device)
-    else:
-        from .engine.mtl import MTLProgram
-        prog = MTLProgram(model, batch, device, in_hw=tuple(x.shape[2:]))
-        labels = torch.zeros(n, 2, dtype=torch.int64, device=device)
-    from .engine.tune import autotune_program
-    autotune_program(prog, measure=False)
+    prog = _eval_program(model, model_type, batch, device, tuple(x.shape[2:]))
+    labels = torch.zeros((n,) if model_type == "multi_classifier" else (n, 2), dtype=torch.int64, device=device)
     runner = StepRunner(prog, x, labels, use_graph=True, X_eval=x, labels_eval=labels)
     outs = [[] for _ in range(1 if model_type == "multi_classifier" else prog.T)]
     for i in range(0, n, batch):
@@ -179,19 +169,24 @@ def _engine_probs(model: nn.Module, model_type: str, x: torch.Tensor, batch: int
     return [torch.cat(o) for o in outs]
 
 
+def _eval_program(model: nn.Module, model_type: str, batch: int, device, in_hw):
+    """The lowered program of ``model`` for inputs of ``in_hw``, its launch configurations from the tuned table."""
+    from .engine.tune import autotune_program
+    if model_type == "multi_classifier":
+        from .engine.inception import InceptionProgram
+        prog = InceptionProgram(model, batch, device, in_hw=in_hw, p_drop=0.0)
+    else:
+        from .engine.mtl import MTLProgram
+        prog = MTLProgram(model, batch, device, in_hw=in_hw)
+    autotune_program(prog, measure=False)
+    return prog
+
+
 def window_runner(model: nn.Module, model_type: str, batch: int, device):
     """The lowered eval program of ``model`` and its step runner for resident-recording inference
     (:func:`resident_probs`); one runner serves any number of recordings."""
     from .engine.step import StepRunner
-    from .engine.tune import autotune_program
-    if model_type == "multi_classifier":
-        from .engine.inception import InceptionProgram
-        prog = InceptionProgram(model, batch, device, in_hw=WINDOW, p_drop=0.0)
-    else:
-        from .engine.mtl import MTLProgram
-        prog = MTLProgram(model, batch, device, in_hw=WINDOW)
-    autotune_program(prog, measure=False)
-    return StepRunner(prog, None, None, use_graph=True)
+    return StepRunner(_eval_program(model, model_type, batch, device, WINDOW), None, None, use_graph=True)
 
 
 def resident_probs(runner, rec: torch.Tensor, fs: np.ndarray, ts: np.ndarray, lo: int = 0,
@@ -200,20 +195,21 @@ def resident_probs(runner, rec: torch.Tensor, fs: np.ndarray, ts: np.ndarray, lo
     the other rows are zero.  The recording is uploaded once; every batch is one replay of the runner's inference
     graph, with no host copy between the replays.  A recording of the shape, window starts and range of the
     runner's last one reuses its device buffers and its captured graph."""
+    from .ops.functional import _starts
     prog = runner.p
     dev = prog.device
     n = len(fs) * len(ts)
     hi = n if hi is None else hi
     key = (tuple(rec.shape), tuple(int(v) for v in fs), tuple(int(v) for v in ts))
-    if runner.window is not None and runner.window_key == key:
-        rec_d, fs_d, ts_d, table = runner.window[:4]
+    src = runner.inference.get("infer")
+    if src is not None and src.key == key:
+        rec_d, fs_d, ts_d, table = (src.tensors[k] for k in ("rec", "fs", "ts", "probs"))
         rec_d.copy_(rec)
         table.zero_()
     else:
         runner.clear_window_source()  # the last recording leaves before this one arrives
         rec_d = rec.to(device=dev, dtype=torch.float32, copy=True).contiguous()  # the runner's own buffer
-        fs_d = torch.as_tensor(np.asarray(fs), dtype=torch.int32).to(dev)
-        ts_d = torch.as_tensor(np.asarray(ts), dtype=torch.int32).to(dev)
+        fs_d, ts_d = _starts(fs, dev), _starts(ts, dev)
         table = torch.zeros(n, sum(prog.prob_classes()), device=dev)
     runner.set_window_source(rec_d, fs_d, ts_d, table, lo, hi, key=key)
     for _ in range((hi - lo + prog.B - 1) // prog.B):
@@ -507,7 +503,7 @@ class _EngineLive:
         self.ring = torch.zeros(C, F, R, device=dev)
         self.state = HF.live_state(dev)
         self.table = torch.zeros(jcap * len(fs), K, device=dev)
-        self.fs_d = torch.as_tensor(np.asarray(fs), dtype=torch.int32).to(dev)
+        self.fs_d = HF._starts(fs, dev)
         # one pinned staging buffer and its device twin, reused by every push
         self.stage_h = torch.empty(C * F * (R - window[1]), dtype=torch.float32).pin_memory()
         self.stage_d = torch.empty(C * F * (R - window[1]), dtype=torch.float32, device=dev)

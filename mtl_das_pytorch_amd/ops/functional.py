@@ -707,6 +707,33 @@ def _starts(s, device) -> torch.Tensor:
     return torch.as_tensor(s).to(device=device, dtype=torch.int32).contiguous()
 
 
+def _gather_out(device, fs: torch.Tensor, window: Tuple[int, int], B: int, taps: int, off: int, lab_w: int):
+    """What both window gathers write and share: the bf16 NHWC-8 batch, the labels, and the launch fields of the
+    batch geometry (fiber starts, window, tap packing) and of the two outputs."""
+    out = torch.empty(B, window[0], window[1], 8, device=device, dtype=torch.bfloat16)
+    lab = torch.empty(B, lab_w, device=device, dtype=torch.int64)
+    return ({"fs": ptr(fs), "nf": fs.numel(), "B": B, "Wf": window[0], "Wt": window[1], "taps": taps, "off": off,
+             "out": ptr(out), "lab_out": ptr(lab), "lab_w": lab_w}, out, lab)
+
+
+def _prob_source(src: torch.Tensor, K: int, ncls: Optional[Sequence[int]]):
+    """The source of a probability launch checked against the table's ``K`` columns: the heads' log-probabilities
+    [T, B, 16] with one ``ncls`` per task, or logits [B, K].  Returns ``B`` and the launch fields."""
+    _check(src, torch.float32)
+    if ncls is not None:
+        if src.dim() != 3 or src.shape[2] != 16 or src.shape[0] != len(ncls):
+            raise ValueError("log-probabilities must be [T, B, 16] with one ncls per task")
+        B = src.shape[1]
+    else:
+        if src.dim() != 2 or src.shape[1] != K:
+            raise ValueError("logits must be [B, K]")
+        B = src.shape[0]
+    d = {"B": B, "src": ptr(src), "softmax": int(ncls is None), "K": K}
+    if ncls is not None:
+        d["ncls"] = [int(k) for k in ncls]
+    return B, d
+
+
 def gather_windows(rec: torch.Tensor, fs, ts, window: Tuple[int, int], B: int, idx: Optional[torch.Tensor] = None,
                    cursor: Optional[torch.Tensor] = None, lo: int = 0, hi: Optional[int] = None, taps: int = 0,
                    off: int = 0, lab_w: int = 2):
@@ -728,12 +755,10 @@ def gather_windows(rec: torch.Tensor, fs, ts, window: Tuple[int, int], B: int, i
     if idx is not None and idx.numel() != B:
         raise ValueError("idx must hold B window numbers")
     hi = fs.numel() * ts.numel() if hi is None else hi
-    out = torch.empty(B, window[0], window[1], 8, device=rec.device, dtype=torch.bfloat16)
-    lab = torch.empty(B, lab_w, device=rec.device, dtype=torch.int64)
-    lib().gather_windows(stream(), {"rec": ptr(rec), "fs": ptr(fs), "ts": ptr(ts), "C": C, "F": Fn, "T": Tn,
-                                    "nf": fs.numel(), "nt": ts.numel(), "B": B, "Wf": window[0], "Wt": window[1],
-                                    "taps": taps, "off": off, "idx": ptr(idx), "cursor": ptr(cursor), "lo": lo,
-                                    "hi": hi, "out": ptr(out), "lab_out": ptr(lab), "lab_w": lab_w})
+    d, out, lab = _gather_out(rec.device, fs, window, B, taps, off, lab_w)
+    d.update({"rec": ptr(rec), "ts": ptr(ts), "C": C, "F": Fn, "T": Tn, "nt": ts.numel(), "idx": ptr(idx),
+              "cursor": ptr(cursor), "lo": lo, "hi": hi})
+    lib().gather_windows(stream(), d)
     return out, lab
 
 
@@ -745,7 +770,6 @@ def window_probs(src: torch.Tensor, probs: torch.Tensor, idx: Optional[torch.Ten
     (Models A/B): ``src`` is the heads' log-probabilities [T, B, 16] and the table holds ``exp`` of the first
     ``ncls[t]`` columns of every task side by side.  Otherwise (Model C) ``src`` is logits [B, K] and the table holds
     their softmax.  In cursor form the launch advances the cursor by one."""
-    _check(src, torch.float32)
     _check(probs, torch.float32)
     if (idx is None) == (cursor is None):
         raise ValueError("exactly one of idx / cursor")
@@ -753,20 +777,11 @@ def window_probs(src: torch.Tensor, probs: torch.Tensor, idx: Optional[torch.Ten
         if t is not None:
             _check(t, torch.int64)
     N, K = probs.shape
-    if ncls is not None:
-        if src.dim() != 3 or src.shape[2] != 16 or src.shape[0] != len(ncls):
-            raise ValueError("log-probabilities must be [T, B, 16] with one ncls per task")
-        B = src.shape[1]
-    else:
-        if src.dim() != 2 or src.shape[1] != K:
-            raise ValueError("logits must be [B, K]")
-        B = src.shape[0]
+    B, d = _prob_source(src, K, ncls)
     if idx is not None and idx.numel() != B:
         raise ValueError("idx must hold B window numbers")
-    d = {"B": B, "idx": ptr(idx), "cursor": ptr(cursor), "lo": lo, "hi": N if hi is None else hi, "src": ptr(src),
-         "softmax": int(ncls is None), "K": K, "probs": ptr(probs), "nprobs": N}
-    if ncls is not None:
-        d["ncls"] = [int(k) for k in ncls]
+    d.update({"idx": ptr(idx), "cursor": ptr(cursor), "lo": lo, "hi": N if hi is None else hi, "probs": ptr(probs),
+              "nprobs": N})
     lib().window_probs(stream(), d)
     return probs
 
@@ -805,6 +820,12 @@ def _weight_band(w, starts, win: int, cell: int, device) -> torch.Tensor:
     return torch.from_numpy(band.astype(np.float32)).to(device).contiguous()
 
 
+def _axis_tables(starts, win: int, length: int, cell: int, device):
+    """One axis of a map launch: the int32 device start table and the fp32 weight band of its windows."""
+    w = window_cell_weights(starts, win, length, cell)
+    return _starts(starts, device), _weight_band(w, starts, win, cell, device)
+
+
 def window_map(probs: torch.Tensor, fs, ts, shape: Tuple[int, int], window: Tuple[int, int],
                cell: Tuple[int, int]) -> torch.Tensor:
     """Per-window probabilities [len(fs) * len(ts), K] -> cell map [K, ceil(F / cf), ceil(T / ct)] (fp32): a
@@ -817,9 +838,8 @@ def window_map(probs: torch.Tensor, fs, ts, shape: Tuple[int, int], window: Tupl
     if N != len(fs_h) * len(ts_h):
         raise ValueError("probs must have one row per window")
     nfc, ntc = -(-shape[0] // cell[0]), -(-shape[1] // cell[1])
-    fs_d, ts_d = _starts(fs_h, probs.device), _starts(ts_h, probs.device)
-    wf = _weight_band(window_cell_weights(fs_h, window[0], shape[0], cell[0]), fs_h, window[0], cell[0], probs.device)
-    wt = _weight_band(window_cell_weights(ts_h, window[1], shape[1], cell[1]), ts_h, window[1], cell[1], probs.device)
+    fs_d, wf = _axis_tables(fs_h, window[0], shape[0], cell[0], probs.device)
+    ts_d, wt = _axis_tables(ts_h, window[1], shape[1], cell[1], probs.device)
     out = torch.empty(K, nfc, ntc, device=probs.device, dtype=torch.float32)
     lib().window_map(stream(), {"probs": ptr(probs), "fs": ptr(fs_d), "ts": ptr(ts_d), "map": ptr(out), "K": K,
                                 "F": shape[0], "T": shape[1], "Wf": window[0], "Wt": window[1], "cf": cell[0],
@@ -885,10 +905,8 @@ def gather_windows_ring(ring: torch.Tensor, state: torch.Tensor, fs, st: int, wi
     ``avail`` on are zeros.  Returns (bf16 NHWC-8 batch, zero labels)."""
     fs = _starts(fs, ring.device)
     d = _live_args(ring, state, fs.numel(), st, window[1])
-    out = torch.empty(B, window[0], window[1], 8, device=ring.device, dtype=torch.bfloat16)
-    lab = torch.empty(B, lab_w, device=ring.device, dtype=torch.int64)
-    d.update({"fs": ptr(fs), "B": B, "Wf": window[0], "taps": taps, "off": off, "out": ptr(out), "lab_out": ptr(lab),
-              "lab_w": lab_w})
+    g, out, lab = _gather_out(ring.device, fs, window, B, taps, off, lab_w)
+    d.update(g)
     lib().gather_windows_ring(stream(), d)
     return out, lab
 
@@ -898,7 +916,6 @@ def live_probs(src: torch.Tensor, table: torch.Tensor, state: torch.Tensor, nf: 
     """:func:`window_probs` for the live numbering: batch row ``r`` is window ``next + r`` = ``(j, a)`` and goes to
     row ``(j mod jcap) * nf + a`` of the ring table ``table`` [>= jcap * nf, K] (in place); rows from ``avail`` on are
     skipped.  The launch then advances ``next`` by the number of valid rows."""
-    _check(src, torch.float32)
     _check(table, torch.float32)
     _check(state, torch.int64)
     if state.numel() != LIVE_NSTATE:
@@ -906,18 +923,8 @@ def live_probs(src: torch.Tensor, table: torch.Tensor, state: torch.Tensor, nf: 
     N, K = table.shape
     if jcap < 1 or nf < 1 or N < jcap * nf:
         raise ValueError(f"a table of {N} rows is below jcap * nf = {jcap * nf}")
-    if ncls is not None:
-        if src.dim() != 3 or src.shape[2] != 16 or src.shape[0] != len(ncls):
-            raise ValueError("log-probabilities must be [T, B, 16] with one ncls per task")
-        B = src.shape[1]
-    else:
-        if src.dim() != 2 or src.shape[1] != K:
-            raise ValueError("logits must be [B, K]")
-        B = src.shape[0]
-    d = {"state": ptr(state), "B": B, "nf": int(nf), "src": ptr(src), "softmax": int(ncls is None), "K": K,
-         "table": ptr(table), "nrows": N, "Jcap": int(jcap)}
-    if ncls is not None:
-        d["ncls"] = [int(k) for k in ncls]
+    _, d = _prob_source(src, K, ncls)
+    d.update({"state": ptr(state), "nf": int(nf), "table": ptr(table), "nrows": N, "Jcap": int(jcap)})
     lib().live_probs(stream(), d)
     return table
 
@@ -944,8 +951,7 @@ def live_map(table: torch.Tensor, fs, F: int, Wf: int, cf: int, jcap: int, jlo, 
     for q, w in enumerate(wt):
         band[q, :len(w)] = np.asarray(w, dtype=np.float64).astype(np.float32)
     dev = table.device
-    fs_d = _starts(fs_h, dev)
-    wf = _weight_band(window_cell_weights(fs_h, Wf, F, cf), fs_h, Wf, cf, dev)
+    fs_d, wf = _axis_tables(fs_h, Wf, F, cf, dev)
     wt_d = torch.from_numpy(band).to(dev)
     jlo_d = torch.as_tensor([int(v) for v in jlo], dtype=torch.int64).to(dev)
     jn_d = torch.as_tensor(jn, dtype=torch.int32).to(dev)

@@ -141,10 +141,16 @@ def test_launchers_refuse_bad_arguments():
     for fn, d in bad:
         with pytest.raises(RuntimeError, match="rc=-2"):
             fn(stream(), d)
-    with pytest.raises(RuntimeError, match="rc=-2"):  # a table below Jcap * nf rows
-        lib().live_map(stream(), {"table": ptr(table), "fs": ptr(fs_d), "map": ptr(out), "wf": ptr(src),
-                                  "wt": ptr(src), "jlo": ptr(lab), "jn": ptr(fs_d), "mf": 4, "mw": 1, "K": 3,
-                                  "F": F_, "Wf": 5, "cf": 2, "nfc": 5, "Jcap": 2, "nrows": 5}, [0, 2, 4], [0], [1])
+    mp = {"table": ptr(table), "fs": ptr(fs_d), "map": ptr(out), "wf": ptr(src), "wt": ptr(src), "jlo": ptr(lab),
+          "jn": ptr(fs_d), "mf": 4, "mw": 1, "K": 3, "F": F_, "Wf": 5, "cf": 2, "nfc": 5, "Jcap": 2, "nrows": 5}
+    bad_maps = [
+        (mp, [0, 2, 4]),                   # a table below Jcap * nf rows
+        (dict(mp, nrows=6), [0, 2, 3]),    # fiber row 8 of F = 9 is in no window
+        (dict(mp, nrows=6), [0, 4, 2]),    # starts not increasing
+    ]
+    for d, fs_h in bad_maps:
+        with pytest.raises(RuntimeError, match="rc=-2"):
+            lib().live_map(stream(), d, fs_h, [0], [1])
     with pytest.raises(ValueError):
         HF.gather_windows_ring(torch.zeros(1, F_, 7, device="cuda"), state, [0, 2, 4], ST, WIN, B)
     torch.cuda.synchronize()
