@@ -5,6 +5,7 @@
         --out predictions.csv --cell 50,125 --map maps.npz
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 infer.py ...   # windows sharded over ranks
     python infer.py ... --chunk 2000 [--ring 4096]   # read and evaluate the recording 2000 time samples at a time
+    python infer.py ... --gate_db 3 [--noise_floor auto|P]   # evaluate only windows 3 dB above the noise floor
 """
 import argparse
 import os
@@ -30,7 +31,23 @@ def main():
                     help="feed the recording to a LiveRecording in chunks of this many time samples (a .npy is "
                          "memory-mapped): the recording need not fit on the device; same CSV and maps")
     ap.add_argument("--ring", type=int, default=None, help="with --chunk: time samples kept on the device")
+    ap.add_argument("--gate_db", type=float, default=None,
+                    help="activity gate: only windows whose power is at least the noise floor + this many dB are "
+                         "evaluated, the others are reported as quiet (pred -1); default: no gate")
+    ap.add_argument("--noise_floor", default="auto",
+                    help="with --gate_db: 'auto' (per fiber position, the lower median of its windows' powers over "
+                         "time) or a power")
     args = ap.parse_args()
+    if args.gate_db is not None and args.chunk is not None:
+        ap.error("--gate_db cannot be combined with --chunk: a growing recording has no activity gate")
+    noise_floor = args.noise_floor
+    if noise_floor != "auto":
+        try:
+            noise_floor = float(noise_floor)
+        except ValueError:
+            ap.error("--noise_floor must be 'auto' or a power")
+        if args.gate_db is None:
+            ap.error("--noise_floor needs --gate_db")
 
     from mtl_das_pytorch_amd import use_engine_graph_queues
     use_engine_graph_queues()  # before the first HIP call
@@ -67,13 +84,13 @@ def main():
         else:
             rec = np.load(args.recording, allow_pickle=False).astype(np.float32)
         res = predict_recording(model, args.model, torch.from_numpy(rec), stride=stride, batch=args.batch_size,
-                                ctx=ctx, use_engine=use_engine)
+                                ctx=ctx, use_engine=use_engine, gate_db=args.gate_db, noise_floor=noise_floor)
     if ctx.is_main:
         import pandas as pd
         cols = {"fiber_start": res["positions"][:, 0], "time_start": res["positions"][:, 1]}
-        for k in ("distance_pred", "event_pred", "joint_pred"):
+        for k in ("distance_pred", "event_pred", "joint_pred", "power_db", "active"):
             if k in res:
-                cols[k] = res[k]
+                cols[k] = res[k].astype(np.int64) if k == "active" else res[k]
         pd.DataFrame(cols).to_csv(args.out, index=False)
         print(f"{len(res['positions'])} windows -> {args.out}")
         if args.map:
@@ -87,7 +104,7 @@ def main():
                     [res[k] for k in ("distance_prob", "event_prob") if k in res], 1)
                 if ctx.device.type == "cuda" and use_engine is not False:  # summed on the device; numpy fp64 otherwise
                     probs = torch.from_numpy(probs).to(ctx.device)
-                maps = prediction_map(probs, fs, ts, shape, cell)
+                maps = prediction_map(probs, fs, ts, shape, cell, active=res.get("active"))
             nfc, ntc = next(iter(maps.values())).shape[-2:]
             np.savez(args.map, fiber_edges=np.minimum(np.arange(nfc + 1) * cell[0], shape[0]),
                      time_edges=np.minimum(np.arange(ntc + 1) * cell[1], shape[1]), **maps)

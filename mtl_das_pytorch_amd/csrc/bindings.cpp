@@ -438,6 +438,43 @@ void window_map(int64_t stream, py::dict d, std::vector<int> fs, std::vector<int
   check(launch_window_map(a, fs.data(), ts.data(), S(stream)), "window_map");
 }
 
+void window_power(int64_t stream, py::dict d) {
+  PowerArgs a{};
+  a.rec = P<const float>(d, "rec"); a.fs = P<const int>(d, "fs"); a.ts = P<const int>(d, "ts");
+  a.power = P<float>(d, "power");
+  a.C = (int)I(d, "C"); a.F = (int)I(d, "F"); a.T = (int)I(d, "T"); a.nf = (int)I(d, "nf"); a.nt = (int)I(d, "nt");
+  a.Wf = (int)I(d, "Wf"); a.Wt = (int)I(d, "Wt");
+  check(launch_window_power(a, S(stream)), "window_power");
+}
+
+void select_windows(int64_t stream, py::dict d) {
+  SelectArgs a{};
+  a.power = P<const float>(d, "power"); a.floor = P<const float>(d, "floor"); a.ratio = (float)F(d, "ratio");
+  a.N = I(d, "N"); a.lo = I(d, "lo"); a.hi = I(d, "hi"); a.nfloor = I(d, "nfloor"); a.nt = (int)I(d, "nt");
+  a.active = P<uint8_t>(d, "active"); a.sel = P<int64_t>(d, "sel"); a.cap = I(d, "cap");
+  a.offs = P<int64_t>(d, "offs");
+  check(launch_select_windows(a, P<int64_t>(d, "count"), I(d, "noffs"), S(stream)), "select_windows");
+}
+
+WindowSelArgs parse_window_sel(const py::dict& d) {
+  WindowSelArgs a{};
+  static_cast<WindowArgs&>(a) = parse_window(d);
+  a.sel = P<const int64_t>(d, "sel"); a.count = P<const int64_t>(d, "count"); a.cap = I(d, "cap");
+  return a;
+}
+
+void gather_windows_sel(int64_t stream, py::dict d) {
+  check(launch_gather_windows_sel(parse_window_sel(d), P<bf16_t>(d, "out"), P<int64_t>(d, "lab_out"),
+                                  (int)I(d, "lab_w"), S(stream)), "gather_windows_sel");
+}
+
+void window_probs_sel(int64_t stream, py::dict d) {
+  const std::vector<int> ncls = parse_ncls(d, "window_probs_sel");
+  check(launch_window_probs_sel(parse_window_sel(d), P<const float>(d, "src"), (int)I(d, "softmax"),
+                                (int)ncls.size(), ncls.data(), (int)I(d, "K"), P<float>(d, "probs"), I(d, "nprobs"),
+                                S(stream)), "window_probs_sel");
+}
+
 LiveArgs parse_live(const py::dict& d) {
   LiveArgs a{};
   a.g = parse_geom(d);
@@ -606,6 +643,11 @@ PYBIND11_MODULE(_mda_hip, m) {
   m.def("gather_windows", &gather_windows);
   m.def("window_probs", &window_probs);
   m.def("window_map", &window_map, py::arg("stream"), py::arg("d"), py::arg("fs"), py::arg("ts"));
+  m.def("window_power", &window_power);
+  m.def("select_windows", &select_windows);
+  m.def("select_blocks", &select_blocks);
+  m.def("gather_windows_sel", &gather_windows_sel);
+  m.def("window_probs_sel", &window_probs_sel);
   m.def("ring_append", &ring_append);
   m.def("gather_windows_ring", &gather_windows_ring);
   m.def("live_probs", &live_probs);

@@ -376,6 +376,41 @@ struct MapArgs {
 };
 // h_fs / h_ts: host copies of the start tables, checked to cover [0, F) x [0, T) (-2 otherwise)
 int launch_window_map(const MapArgs& a, const int* h_fs, const int* h_ts, hipStream_t st);
+// gate.hip: the activity gate of resident-recording inference -- the windows' power, the ordered selection of the
+// active ones, and the gather / probability store numbered by that selection
+struct PowerArgs {
+  const float* rec;   // recording [C][F][T] fp32
+  const int* fs;      // window starts [nf], [nt]; window n = a * nt + b
+  const int* ts;
+  float* power;       // [nf * nt]: (1 / C) sum_c mean over the window of (x - the window's mean in c)^2
+  int C, F, T, nf, nt, Wf, Wt;
+};
+int launch_window_power(const PowerArgs& a, hipStream_t st);
+struct SelectArgs {
+  const float* power;  // [N]
+  const float* floor;  // [nfloor >= ceil(N / nt)]: the noise floor of fiber start n / nt
+  float ratio;         // 10^(gate_db / 10): window n of [lo, hi) is active iff !(power[n] < floor[n / nt] * ratio)
+  int64_t N, lo, hi, nfloor;
+  int nt;
+  uint8_t* active;     // [N]: the flags, zero outside [lo, hi)
+  int64_t* sel;        // [cap >= hi - lo]: the active window numbers in ascending order; entries past the count
+  int64_t cap;         // are left untouched
+  int64_t* offs;       // workspace, one entry per block of 256 windows (select_blocks)
+};
+int64_t select_blocks(int64_t N);
+// three launches (flags + block counts, scan of the counts, ranked scatter); count: device int64, the active windows
+int launch_select_windows(const SelectArgs& a, int64_t* count, int64_t noffs, hipStream_t st);
+// WindowArgs in cursor form with the batch rows numbered by a selection: in replay *cursor, row r holds window
+// sel[*cursor * B + r] while *cursor * B + r < min(*count, cap), and is padding beyond (or where that window number
+// is outside [lo, hi)): gathered as zeros, skipped by the store, which advances the cursor
+struct WindowSelArgs : WindowArgs {
+  const int64_t* sel;
+  const int64_t* count;  // device scalar, read by every replay
+  int64_t cap;           // entries of sel
+};
+int launch_gather_windows_sel(const WindowSelArgs& a, bf16_t* out, int64_t* lab_out, int lab_w, hipStream_t st);
+int launch_window_probs_sel(const WindowSelArgs& a, const float* src, int softmax, int T, const int* ncls, int K,
+                            float* probs, int64_t nprobs, hipStream_t st);
 // live.hip: inference on a growing recording -- the time axis as a ring of R columns, windows numbered time-major
 // (n = j * nf + a: time index j starts at j * st), probabilities into a ring table, final map columns
 enum { LIVE_TOTAL = 0, LIVE_AVAIL, LIVE_NEXT, LIVE_JEND, LIVE_TEND, LIVE_NSTATE };

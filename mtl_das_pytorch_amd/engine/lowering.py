@@ -8,7 +8,7 @@ from typing import Callable, Dict, List, Optional
 
 import torch
 
-from ..ops.functional import LIVE_NSTATE, WGRAD_PATCH, WGRAD_TILES, noise_args, wgrad_ktiles
+from ..ops.functional import LIVE_NSTATE, WGRAD_PATCH, WGRAD_TILES, noise_args, selection_args, wgrad_ktiles
 from ..ops.hip import lib
 from .core import (GRAD_DT, Act, BNLayer, ConvLayer, P, build_optseg_table, build_wgfin_table, optimizer_segments,
                    pad_to)
@@ -17,6 +17,7 @@ from .program import (COMM_STREAM, SPILL_STREAM, Launch, Phase, k_adam, k_step_i
                       k_wgrad_batched, k_window_probs)
 from .program import NoiseSpec, k_gather_noise, k_noise_advance
 from .program import k_gather_windows_ring, k_live_probs
+from .program import k_gather_windows_sel, k_window_probs_sel
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID, SIGMUL, ADD_RELU, POOL_RELU = range(6)
 
@@ -462,21 +463,29 @@ class LoweredProgram:
                 "Wt": self.W0, "taps": self.stem_pack[0], "off": self.stem_pack[1], "out": P(self.x),
                 "lab_out": P(self.labels), "lab_w": self.label_width}
 
-    def window_gather_phase(self, rec, fs, ts, idx=None, cursor=None, lo: int = 0, hi: Optional[int] = None) -> Phase:
+    def window_gather_phase(self, rec, fs, ts, idx=None, cursor=None, lo: int = 0, hi: Optional[int] = None,
+                            sel=None, count=None) -> Phase:
         """The batch gather of resident-recording inference: the batch's (H0, W0) windows are cut from ``rec``
         ([C, F, T] fp32 on the device) into the stem's input, labels zeroed.  ``fs`` / ``ts``: int32 device
         tables of the window starts, window ``n = a * len(ts) + b``; batch row ``r`` is window ``idx[r]`` or
         ``lo + cursor * B + r`` (``cursor``: a device int64 scalar that window_probs_phase advances); rows whose
-        window number is outside ``[lo, hi)`` are zeros."""
+        window number is outside ``[lo, hi)`` are zeros.  ``sel`` / ``count`` (with ``cursor``, without ``idx``): an
+        on-device selection (csrc/gate.hip) -- row ``r`` is window ``sel[cursor * B + r]`` while that entry is
+        below ``count`` (a device int64 scalar, read by every replay), zeros beyond."""
         self._window_source(rec, "recording")
         for t in (fs, ts):
             self._device_vector(t, torch.int32, "a window-start table")
         d = self._window_args(idx, cursor, lo, fs.numel() * ts.numel() if hi is None else hi)
         d.update(self._stem_fields(rec, fs))
         d.update({"rec": P(rec), "ts": P(ts), "T": rec.shape[2], "nt": ts.numel()})
+        s = selection_args(sel, count, idx, cursor)
+        d.update(s)
         ph = Phase("window_gather")
-        ph.add("gather_windows", k_gather_windows, d)
-        ph.keep = (rec, fs, ts, idx, cursor)  # the launch holds their device pointers
+        if s:
+            ph.add("gather_windows_sel", k_gather_windows_sel, d)
+        else:
+            ph.add("gather_windows", k_gather_windows, d)
+        ph.keep = (rec, fs, ts, idx, cursor, sel, count)  # the launch holds their device pointers
         return ph
 
     def prob_classes(self) -> List[int]:
@@ -499,16 +508,23 @@ class LoweredProgram:
             d["ncls"] = ncls
         return d
 
-    def window_probs_phase(self, probs, idx=None, cursor=None, lo: int = 0, hi: Optional[int] = None) -> Phase:
+    def window_probs_phase(self, probs, idx=None, cursor=None, lo: int = 0, hi: Optional[int] = None, sel=None,
+                           count=None) -> Phase:
         """After ``fwd_eval``: the batch's probabilities into rows of the resident table ``probs`` [N, K] (fp32) --
         ``exp`` of the heads' log-probabilities, or the softmax of Model C's logits -- for the batch rows whose
-        window number is in ``[lo, hi)``; in cursor form the launch then advances the cursor by one."""
+        window number is in ``[lo, hi)``; in cursor form the launch then advances the cursor by one.  ``sel`` /
+        ``count``: the rows are numbered by the selection, as in :meth:`window_gather_phase`."""
         d = self._prob_fields(probs)
         d.update(self._window_args(idx, cursor, lo, probs.shape[0] if hi is None else hi))
         d.update({"probs": P(probs), "nprobs": probs.shape[0]})
+        s = selection_args(sel, count, idx, cursor)
+        d.update(s)
         ph = Phase("window_probs")
-        ph.add("window_probs", k_window_probs, d)
-        ph.keep = (probs, idx, cursor)
+        if s:
+            ph.add("window_probs_sel", k_window_probs_sel, d)
+        else:
+            ph.add("window_probs", k_window_probs, d)
+        ph.keep = (probs, idx, cursor, sel, count)
         return ph
 
     def live_gather_phase(self, ring, fs, state, st: int) -> Phase:

@@ -427,6 +427,16 @@ def k_window_probs(d, st):
     lib().window_probs(st, d)
 
 
+def k_gather_windows_sel(d, st):
+    """The batch's windows by an on-device selection (csrc/gate.hip): row r is window sel[cursor * B + r]."""
+    lib().gather_windows_sel(st, d)
+
+
+def k_window_probs_sel(d, st):
+    """The selected batch rows' probabilities into the resident table; advances the batch cursor."""
+    lib().window_probs_sel(st, d)
+
+
 def k_gather_windows_ring(d, st):
     """The batch's windows cut from the time ring of a live recording (csrc/live.hip)."""
     lib().gather_windows_ring(st, d)

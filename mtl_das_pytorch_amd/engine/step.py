@@ -83,13 +83,15 @@ class InferSource:
     key: object = None                # what the source's owner knows it by (inference.resident_probs)
 
     def same(self, o: "InferSource") -> bool:
-        return all(t is o.tensors[k] for k, t in self.tensors.items()) and self.consts == o.consts
+        return (self.tensors.keys() == o.tensors.keys() and all(t is o.tensors[k] for k, t in self.tensors.items())
+                and self.consts == o.consts)
 
 
 def _window_phases(p, s: InferSource):
     t = s.tensors
-    return (p.window_gather_phase(t["rec"], t["fs"], t["ts"], cursor=t["cursor"], **s.consts),
-            p.window_probs_phase(t["probs"], cursor=t["cursor"], **s.consts))
+    by = {k: t[k] for k in ("sel", "count") if k in t}  # a gated source: rows numbered by the selection
+    return (p.window_gather_phase(t["rec"], t["fs"], t["ts"], cursor=t["cursor"], **s.consts, **by),
+            p.window_probs_phase(t["probs"], cursor=t["cursor"], **s.consts, **by))
 
 
 def _live_phases(p, s: InferSource):
@@ -377,24 +379,34 @@ class StepRunner:
         self._run("eval")
 
     def set_window_source(self, rec: torch.Tensor, fs: torch.Tensor, ts: torch.Tensor, probs: torch.Tensor,
-                          lo: int = 0, hi: Optional[int] = None, key=None):
+                          lo: int = 0, hi: Optional[int] = None, key=None, sel: Optional[torch.Tensor] = None,
+                          count: Optional[torch.Tensor] = None):
         """Resident-recording inference: ``infer_step()`` then evaluates the next ``B`` windows of ``[lo, hi)`` --
         cut on the device from ``rec`` [C, F, T] at the starts ``fs`` x ``ts`` (int32 device tables, window
         ``n = a * len(ts) + b``) -- and writes their probabilities into rows of ``probs`` [N, K]; the step's last
         kernel advances the batch cursor, so ceil((hi - lo) / B) calls cover the range with no host copy between
         them.  The cursor restarts at ``lo``.  Other tensors or another range rebuild the captured graph (its
         launches hold the device pointers and the range).  ``key``: kept as the source's ``key`` until it is
-        replaced or cleared -- how a caller that uploaded the tensors recognises them again."""
+        replaced or cleared -- how a caller that uploaded the tensors recognises them again.
+
+        ``sel`` / ``count`` (together): an on-device selection (ops.functional.select_windows) -- ``infer_step()``
+        then evaluates the next ``B`` entries of ``sel`` (int64 window numbers of ``[lo, hi)``) below ``count``, a
+        device int64 scalar that every replay reads: ceil(count / B) calls cover the selection, whatever it is, with
+        one captured graph.  The two tensors are part of the source like the others."""
         hi = fs.numel() * ts.numel() if hi is None else hi
         if probs.shape[0] != fs.numel() * ts.numel():
             raise ValueError("the probability table needs one row per window")
         if not 0 <= lo <= hi <= probs.shape[0]:
             raise ValueError(f"window range [{lo}, {hi}) outside the {probs.shape[0]} windows")
+        if (sel is None) != (count is None):
+            raise ValueError("a selection is sel and count together")
         if self.window_cursor is None:
             self.window_cursor = torch.zeros(1, dtype=torch.int64, device=self.p.device)
-        self._set_source("infer", InferSource({"rec": rec, "fs": fs, "ts": ts, "probs": probs,
-                                               "cursor": self.window_cursor}, {"lo": int(lo), "hi": int(hi)},
-                                              ("cursor", "probs"), _window_phases)).key = key
+        tensors = {"rec": rec, "fs": fs, "ts": ts, "probs": probs, "cursor": self.window_cursor}
+        if sel is not None:
+            tensors.update(sel=sel, count=count)
+        self._set_source("infer", InferSource(tensors, {"lo": int(lo), "hi": int(hi)}, ("cursor", "probs"),
+                                              _window_phases)).key = key
         self.window_cursor.zero_()
 
     def clear_window_source(self):

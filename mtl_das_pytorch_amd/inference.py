@@ -15,6 +15,10 @@ graph, and the window stack -- (100 * 250) / (stride_f * stride_t) times the rec
 :func:`prediction_map` averages the overlapping windows' probabilities into an event-probability and distance
 map along the fiber over time.
 
+The models have no "nothing is happening" class.  ``predict_recording(gate_db=...)`` puts an energy detector in front
+of them: the windows' power is measured (on the engine path on the device, csrc/gate.hip), those below the noise
+floor by the gate are reported as quiet and only the others are evaluated.
+
 :class:`LiveRecording` serves a recording that is still growing: chunks of time samples go into a ring, the windows
 that became available are evaluated by replays of one graph, and map columns are returned as they become final
 (csrc/live.hip on the engine path, a host ring and the fp32 module elsewhere).
@@ -73,17 +77,69 @@ def _torch_probs(model: nn.Module, model_type: str, x: torch.Tensor) -> Sequence
     return [o.exp() for o in outs]  # A/B heads emit log-probabilities
 
 
+def window_power_reference(rec, fs, ts, window: Tuple[int, int] = WINDOW) -> np.ndarray:
+    """fp64 power [len(fs) * len(ts)] of the windows of ``rec`` ([F, T] or [C, F, T]; window ``n = a * len(ts) + b``
+    at ``(fs[a], ts[b])``): the mean over the channels of the mean over the window of ``(x - mu_c)^2``, ``mu_c``
+    the window's own mean in channel ``c`` -- the power of data/noise.py applied to a window.  This is the
+    definition; csrc/gate.hip evaluates it on the device."""
+    x = rec.detach().cpu().numpy() if isinstance(rec, torch.Tensor) else np.asarray(rec)
+    x = x.astype(np.float64)
+    if x.ndim == 2:
+        x = x[None]
+    out = np.empty((len(fs), len(ts)))
+    for a, f0 in enumerate(fs):
+        for b, t0 in enumerate(ts):
+            w = x[:, int(f0):int(f0) + window[0], int(t0):int(t0) + window[1]]
+            out[a, b] = ((w - w.mean((1, 2), keepdims=True)) ** 2).mean()  # equal planes: the mean of the means
+    return out.reshape(-1)
+
+
+def noise_floor_reference(power: np.ndarray, nt: int, noise_floor="auto") -> np.ndarray:
+    """The noise floor of every fiber start, fp64 [nf]: a number is one floor for all of them; ``"auto"`` is the lower
+    median over time of the start's window powers, ``sorted(power[a, :])[(nt - 1) // 2]`` (noise varies along a
+    fiber, and an event is short against a recording)."""
+    p = np.asarray(power, dtype=np.float64).reshape(-1, nt)
+    if isinstance(noise_floor, str):
+        if noise_floor != "auto":
+            raise ValueError(f"noise_floor must be 'auto' or a power, got {noise_floor!r}")
+        return np.sort(p, 1)[:, (nt - 1) // 2]
+    return np.full(len(p), float(noise_floor))
+
+
+def active_reference(power: np.ndarray, nt: int, gate_db: float, noise_floor="auto") -> np.ndarray:
+    """The gate's flags in fp64, bool [N]: window ``n`` is active unless its power is below the floor of its fiber
+    start times ``10^(gate_db / 10)``; a NaN power is active (never hidden)."""
+    p = np.asarray(power, dtype=np.float64)
+    thr = np.repeat(noise_floor_reference(p, nt, noise_floor), nt) * 10.0 ** (float(gate_db) / 10.0)
+    return ~(p < thr)
+
+
+def _power_db(power: np.ndarray) -> np.ndarray:
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return 10.0 * np.log10(np.asarray(power, dtype=np.float64))
+
+
 @torch.no_grad()
 def predict_recording(model: nn.Module, model_type: str, rec: torch.Tensor, stride=(100, 125), batch: int = 32,
                       ctx: Optional[DistContext] = None, device=None, use_engine: Optional[bool] = None,
-                      windows: Optional[str] = None, runner=None) -> Dict:
+                      windows: Optional[str] = None, runner=None, gate_db: Optional[float] = None,
+                      noise_floor="auto") -> Dict:
     """Per-window predictions for one recording.  Returns numpy arrays: ``positions`` [N, 2], and per task
     (``distance`` / ``event`` as the model provides) ``<task>_pred`` [N] and ``<task>_prob`` [N, k].
 
     ``windows``: ``"resident"`` (the engine path's default) uploads the recording once and cuts the windows on
     the device; ``"materialize"`` (the torch backend's only form) builds the window stack on the host.
     ``runner``: a :func:`window_runner` of this model to reuse over many recordings (resident windows only; its
-    batch size holds); without one the call lowers the model itself."""
+    batch size holds); without one the call lowers the model itself.
+
+    ``gate_db``: an energy detector in front of the model, which has no "nothing is happening" class.  A window is
+    active unless its power (:func:`window_power_reference`) is below ``noise_floor`` times ``10^(gate_db / 10)``;
+    only active windows are evaluated.  ``noise_floor``: a power, or ``"auto"``: per fiber start the lower median
+    of its windows' powers over time.  The result gains ``active`` [N] bool and ``power_db`` [N]; a quiet window has
+    ``<task>_pred`` -1 (Model C's decoded ``distance_pred`` / ``event_pred`` too) and a zero ``<task>_prob`` row.
+    On the resident path power, floor, selection and the evaluation of the selected windows run on the device
+    (csrc/gate.hip); every rank computes all flags and gates its own shard.  None: no gate, every window
+    evaluated."""
     device = torch.device(device) if device is not None else (ctx.device if ctx else torch.device("cpu"))
     if use_engine is None:
         use_engine = device.type == "cuda"
@@ -102,16 +158,38 @@ def predict_recording(model: nn.Module, model_type: str, rec: torch.Tensor, stri
         pos = np.stack(np.meshgrid(fs, ts, indexing="ij"), -1).reshape(-1, 2)
         n = len(pos)
         lo, hi = _shard(n, ctx)
+        gate = None if gate_db is None else (float(gate_db), noise_floor)
         if runner is not None:
-            table = resident_probs(runner, rec3, fs, ts, lo, hi)
+            table = resident_probs(runner, rec3, fs, ts, lo, hi, gate=gate)
         else:
-            table = _resident_probs(model, model_type, rec3, fs, ts, lo, hi, batch, device)
+            table = _resident_probs(model, model_type, rec3, fs, ts, lo, hi, batch, device, gate)
+        flags = None
+        if gate is not None:
+            table, active, power = table
+            flags = (active.cpu().numpy().astype(bool), power.cpu().numpy())
         probs = [p.contiguous() for p in table.split(ncls, 1)]
-        return _result(model_type, names, probs, pos, ctx)
-    tiles, pos = sliding_windows(rec.float(), stride=stride)
-    n = len(tiles)
-    lo, hi = _shard(n, ctx)
-    mine = tiles[lo:hi].to(device)
+        return _result(model_type, names, probs, pos, ctx, flags)
+    flags = None
+    if gate_db is not None:
+        # the same gate by the fp64 reference; only the active windows of this rank's shard are stacked
+        rec3 = rec.float().unsqueeze(0) if rec.dim() == 2 else rec.float()
+        fs, ts = window_starts(rec3.shape[1], WINDOW[0], stride[0]), window_starts(rec3.shape[2], WINDOW[1], stride[1])
+        pos = np.stack(np.meshgrid(fs, ts, indexing="ij"), -1).reshape(-1, 2)
+        n = len(pos)
+        lo, hi = _shard(n, ctx)
+        power = window_power_reference(rec3, fs, ts)
+        flags = (active_reference(power, len(ts), gate_db, noise_floor), power)
+        keep = lo + np.flatnonzero(flags[0][lo:hi])
+        rows = torch.from_numpy(keep).to(device)
+        mine = torch.zeros(0)
+        if len(keep):
+            mine = torch.stack([rec3[:, f0:f0 + WINDOW[0], t0:t0 + WINDOW[1]] for f0, t0 in pos[keep]]).to(device)
+    else:
+        tiles, pos = sliding_windows(rec.float(), stride=stride)
+        n = len(tiles)
+        lo, hi = _shard(n, ctx)
+        rows = slice(lo, hi)
+        mine = tiles[lo:hi].to(device)
     probs = [torch.zeros(n, k, device=device) for k in ncls]
     if len(mine):
         if use_engine:
@@ -124,12 +202,13 @@ def predict_recording(model: nn.Module, model_type: str, rec: torch.Tensor, stri
                     chunks[t].append(p)
             chunks = [torch.cat(c) for c in chunks]
         for t in range(len(names)):
-            probs[t][lo:hi] = chunks[t].float()
-    return _result(model_type, names, probs, pos, ctx)
+            probs[t][rows] = chunks[t].float()
+    return _result(model_type, names, probs, pos, ctx, flags)
 
 
-def _result(model_type: str, names, probs, pos, ctx: Optional[DistContext]) -> Dict:
-    """The result dict from the per-task probability tables (each rank filled its own rows of a zeroed table)."""
+def _result(model_type: str, names, probs, pos, ctx: Optional[DistContext], flags=None) -> Dict:
+    """The result dict from the per-task probability tables (each rank filled its own rows of a zeroed table).
+    ``flags``: a gated call's (active [N] bool, power [N]), the same on every rank: quiet windows predict -1."""
     if ctx is not None and ctx.enabled:  # every rank wrote its own rows; the sum is the gather
         for p in probs:
             ctx.all_reduce_(p)
@@ -143,6 +222,11 @@ def _result(model_type: str, names, probs, pos, ctx: Optional[DistContext]) -> D
         for t, name in enumerate(names):
             res[f"{name}_pred"] = probs[t].argmax(1).cpu().numpy()
             res[f"{name}_prob"] = probs[t].cpu().numpy()
+    if flags is not None:
+        active, power = flags
+        for k in [k for k in res if k.endswith("_pred")]:
+            res[k] = np.where(active, res[k], -1)
+        res["active"], res["power_db"] = active, _power_db(power)
     return res
 
 
@@ -190,38 +274,67 @@ def window_runner(model: nn.Module, model_type: str, batch: int, device):
 
 
 def resident_probs(runner, rec: torch.Tensor, fs: np.ndarray, ts: np.ndarray, lo: int = 0,
-                   hi: Optional[int] = None) -> torch.Tensor:
+                   hi: Optional[int] = None, gate=None):
     """Probabilities [N, K] (the tasks side by side) of windows ``[lo, hi)`` of the recording ``rec`` [C, F, T];
     the other rows are zero.  The recording is uploaded once; every batch is one replay of the runner's inference
     graph, with no host copy between the replays.  A recording of the shape, window starts and range of the
-    runner's last one reuses its device buffers and its captured graph."""
-    from .ops.functional import _starts
+    runner's last one reuses its device buffers and its captured graph.
+
+    ``gate`` = (gate_db, noise_floor) (:func:`predict_recording`): returns ``(table, active, power)``.  On the
+    device: the power of all N windows, the floor, the ordered selection of the active windows of ``[lo, hi)``;
+    their number is read back once (8 bytes) and the graph -- whose rows are numbered by the selection, the count
+    read on the device -- is replayed ceil(count / B) times.  The rows of quiet windows stay zero; ``active`` is
+    uint8 [N] over all windows, whatever the range."""
+    from .ops import functional as HF
     prog = runner.p
     dev = prog.device
     n = len(fs) * len(ts)
     hi = n if hi is None else hi
-    key = (tuple(rec.shape), tuple(int(v) for v in fs), tuple(int(v) for v in ts))
+    key = (tuple(rec.shape), tuple(int(v) for v in fs), tuple(int(v) for v in ts)) + (("gated",) if gate else ())
     src = runner.inference.get("infer")
     if src is not None and src.key == key:
         rec_d, fs_d, ts_d, table = (src.tensors[k] for k in ("rec", "fs", "ts", "probs"))
+        sel, count = src.tensors.get("sel"), src.tensors.get("count")
         rec_d.copy_(rec)
         table.zero_()
     else:
         runner.clear_window_source()  # the last recording leaves before this one arrives
         rec_d = rec.to(device=dev, dtype=torch.float32, copy=True).contiguous()  # the runner's own buffer
-        fs_d, ts_d = _starts(fs, dev), _starts(ts, dev)
+        fs_d, ts_d = HF._starts(fs, dev), HF._starts(ts, dev)
         table = torch.zeros(n, sum(prog.prob_classes()), device=dev)
-    runner.set_window_source(rec_d, fs_d, ts_d, table, lo, hi, key=key)
-    for _ in range((hi - lo + prog.B - 1) // prog.B):
+        sel = count = None
+        if gate is not None:
+            sel = torch.empty(n, dtype=torch.int64, device=dev)
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+    if gate is None:
+        runner.set_window_source(rec_d, fs_d, ts_d, table, lo, hi, key=key)
+        for _ in range((hi - lo + prog.B - 1) // prog.B):
+            runner.infer_step()
+        return table.clone()
+    gate_db, noise_floor = gate
+    nf, nt = len(fs), len(ts)
+    power = HF.window_power(rec_d, fs_d, ts_d, WINDOW)
+    if isinstance(noise_floor, str):
+        if noise_floor != "auto":
+            raise ValueError(f"noise_floor must be 'auto' or a power, got {noise_floor!r}")
+        floor = torch.sort(power.view(nf, nt), 1).values[:, (nt - 1) // 2].contiguous()
+    else:
+        floor = torch.full((nf,), float(noise_floor), dtype=torch.float32, device=dev)
+    _, _, active = HF.select_windows(power, floor, gate_db, nt, lo, hi, sel=sel, count=count)
+    if (lo, hi) != (0, n):  # a shard: the selection is this range's, the flags are every window's on every rank
+        active = HF.select_windows(power, floor, gate_db, nt, 0, n)[2]
+    runner.set_window_source(rec_d, fs_d, ts_d, table, lo, hi, key=key, sel=sel, count=count)
+    m = int(count.item())  # the one read-back
+    for _ in range((m + prog.B - 1) // prog.B):
         runner.infer_step()
-    return table.clone()
+    return table.clone(), active, power
 
 
 def _resident_probs(model: nn.Module, model_type: str, rec: torch.Tensor, fs, ts, lo: int, hi: int, batch: int,
-                    device) -> torch.Tensor:
+                    device, gate=None):
     runner = window_runner(model, model_type, batch, device)
     try:
-        return resident_probs(runner, rec, fs, ts, lo, hi)
+        return resident_probs(runner, rec, fs, ts, lo, hi, gate=gate)
     finally:
         runner.close()
 
@@ -243,7 +356,7 @@ def window_map_reference(probs: np.ndarray, fs, ts, shape: Tuple[int, int], cell
 
 
 def prediction_map(res_or_probs, fs, ts, shape: Tuple[int, int], cell: Tuple[int, int],
-                   window: Tuple[int, int] = WINDOW) -> Dict:
+                   window: Tuple[int, int] = WINDOW, active=None) -> Dict:
     """What an operator reads: cells of ``cell`` = (cf, ct) samples along the fiber and time of a recording of
     ``shape`` = (F, T).  A sample's probability is the mean over the windows that cover it, a cell's the mean over
     its samples.
@@ -252,22 +365,48 @@ def prediction_map(res_or_probs, fs, ts, shape: Tuple[int, int], cell: Tuple[int
     and event side by side, 16, 2, or Model C's 32 joint classes, marginalised by ``decode_joint``'s coding
     ``joint = distance + 16 * event``) as an array or a tensor.  A tensor on the GPU is aggregated there (HIP),
     anything else in numpy fp64.  Returns ``event_map`` [2, nfc, ntc], ``distance_map`` [16, nfc, ntc] and
-    ``distance_mean_m`` [nfc, ntc] (1 class = 1 m), as far as the model has the task."""
+    ``distance_mean_m`` [nfc, ntc] (1 class = 1 m), as far as the model has the task.
+
+    ``active``: the flags [N] of a gated :func:`predict_recording` (taken from a result dict that has them).  Only
+    active windows speak: the result gains ``activity_map`` [nfc, ntc], the window-weighted mean of the flags, and
+    every class map is ``sum w p / sum w active`` over the active windows covering the cell -- NaN where the activity
+    is 0, a cell nothing was said about.  The flag column rides along as class K + 1 of one map computation (on the
+    device: one ``window_map`` launch); the division runs after it."""
     if isinstance(res_or_probs, dict):
         r = res_or_probs
         if "joint_prob" in r:
             table = r["joint_prob"]
         else:
             table = np.concatenate([r[k] for k in ("distance_prob", "event_prob") if k in r], 1)
+        if active is None:
+            active = r.get("active")
     else:
         table = res_or_probs
-    if isinstance(table, torch.Tensor) and table.is_cuda:
+    on_device = isinstance(table, torch.Tensor) and table.is_cuda
+    if active is not None:
+        if on_device:
+            flag = torch.as_tensor(active).to(table.device).reshape(-1, 1).float()
+            table = torch.cat([table.float() * flag, flag], 1)
+        else:
+            table = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+            flag = (active.detach().cpu().numpy() if isinstance(active, torch.Tensor) else np.asarray(active))
+            flag = flag.reshape(-1, 1).astype(np.float64)
+            table = np.concatenate([table.astype(np.float64) * flag, flag], 1)
+    if on_device:
         from .ops import functional as HF
-        m = HF.window_map(table.float().contiguous(), fs, ts, shape, window, cell).cpu().numpy().astype(np.float64)
+        m = HF.window_map(table.float().contiguous(), fs, ts, shape, window, cell)
+        if active is not None:
+            m[:-1] = torch.where(m[-1] > 0, m[:-1] / m[-1], torch.full_like(m[:-1], float("nan")))
+        m = m.cpu().numpy().astype(np.float64)
     else:
         table = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table
         m = window_map_reference(table, fs, ts, shape, cell, window)
-    return _task_maps(m)
+        if active is not None:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                m[:-1] = np.where(m[-1] > 0, m[:-1] / m[-1], np.nan)
+    if active is None:
+        return _task_maps(m)
+    return dict(_task_maps(m[:-1]), activity_map=m[-1])
 
 
 def _task_maps(m: np.ndarray) -> Dict:
@@ -570,7 +709,10 @@ class LiveRecording:
     ``table_indices``: time indices the probability table holds (default: enough for any push); a push that would
     overwrite rows still needed raises before it changes anything.  On the engine backend the ring, the window
     counters and the table live on the device and every batch is one replay of one graph captured at construction
-    (``captures`` stays at 1); the torch backend keeps a host ring and evaluates the module in fp32."""
+    (``captures`` stays at 1); the torch backend keeps a host ring and evaluates the module in fp32.
+
+    There is no activity gate here (``predict_recording(gate_db=...)``): every window is evaluated.  Gating a growing
+    recording needs a noise floor that runs along with the stream, which is a change of its own."""
 
     def __init__(self, model: nn.Module, model_type: str, F: int, C: int = 1, stride=(100, 125), cell=None,
                  ring: int = 8 * WINDOW[1], batch: int = 32, device=None, use_engine: Optional[bool] = None,

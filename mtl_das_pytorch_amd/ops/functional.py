@@ -734,14 +734,34 @@ def _prob_source(src: torch.Tensor, K: int, ncls: Optional[Sequence[int]]):
     return B, d
 
 
+def selection_args(sel: Optional[torch.Tensor], count: Optional[torch.Tensor], idx, cursor) -> dict:
+    """The launch fields of a selected window launch (csrc/gate.hip), empty without a selection: ``sel`` (device
+    int64 window numbers) and ``count`` (device int64 scalar, how many of them are valid) come together, with a
+    ``cursor`` and without ``idx``."""
+    if sel is None and count is None:
+        return {}
+    if sel is None or count is None or idx is not None or cursor is None:
+        raise ValueError("a selection is sel and count together, with a cursor and without idx")
+    for t in (sel, count):
+        if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("sel / count must be contiguous int64 tensors on the device")
+    if sel.dim() != 1 or count.numel() != 1:
+        raise ValueError("sel must be a vector and count one number")
+    return {"sel": ptr(sel), "count": ptr(count), "cap": sel.numel()}
+
+
 def gather_windows(rec: torch.Tensor, fs, ts, window: Tuple[int, int], B: int, idx: Optional[torch.Tensor] = None,
                    cursor: Optional[torch.Tensor] = None, lo: int = 0, hi: Optional[int] = None, taps: int = 0,
-                   off: int = 0, lab_w: int = 2):
+                   off: int = 0, lab_w: int = 2, sel: Optional[torch.Tensor] = None,
+                   count: Optional[torch.Tensor] = None):
     """Windows of an HBM-resident recording ``rec`` [C, F, T] (fp32) -> (bf16 NHWC batch with C padded to 8, zero
     labels), the layout of :func:`gather_batch` of the materialised windows.  Window ``n = a * len(ts) + b`` starts
     at ``(fs[a], ts[b])``; batch row ``r`` holds window ``idx[r]`` (int64 [B]) or ``lo + cursor * B + r`` (``cursor``:
     a device int64 scalar).  Rows whose window number is outside ``[lo, hi)`` are zeros.  ``taps`` / ``off``: the
-    1-channel stem's vertical tap packing, padded at the window's edges."""
+    1-channel stem's vertical tap packing, padded at the window's edges.
+
+    ``sel`` / ``count`` (with ``cursor``; :func:`select_windows`): batch row ``r`` holds window
+    ``sel[cursor * B + r]`` while ``cursor * B + r < count``, and is zeros beyond."""
     _check(rec, torch.float32)
     if rec.dim() != 3:
         raise ValueError("recording must be [C, F, T]")
@@ -758,18 +778,27 @@ def gather_windows(rec: torch.Tensor, fs, ts, window: Tuple[int, int], B: int, i
     d, out, lab = _gather_out(rec.device, fs, window, B, taps, off, lab_w)
     d.update({"rec": ptr(rec), "ts": ptr(ts), "C": C, "F": Fn, "T": Tn, "nt": ts.numel(), "idx": ptr(idx),
               "cursor": ptr(cursor), "lo": lo, "hi": hi})
-    lib().gather_windows(stream(), d)
+    s = selection_args(sel, count, idx, cursor)
+    if s:
+        d.update(s)
+        lib().gather_windows_sel(stream(), d)
+    else:
+        lib().gather_windows(stream(), d)
     return out, lab
 
 
 def window_probs(src: torch.Tensor, probs: torch.Tensor, idx: Optional[torch.Tensor] = None,
                  cursor: Optional[torch.Tensor] = None, lo: int = 0, hi: Optional[int] = None,
-                 ncls: Optional[Sequence[int]] = None) -> torch.Tensor:
+                 ncls: Optional[Sequence[int]] = None, sel: Optional[torch.Tensor] = None,
+                 count: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The batch's class probabilities into the resident table ``probs`` [N, K] (fp32, in place): row ``r`` of the
     batch goes to row ``idx[r]`` / ``lo + cursor * B + r``; rows outside ``[lo, hi)`` are skipped.  ``ncls`` given
     (Models A/B): ``src`` is the heads' log-probabilities [T, B, 16] and the table holds ``exp`` of the first
     ``ncls[t]`` columns of every task side by side.  Otherwise (Model C) ``src`` is logits [B, K] and the table holds
-    their softmax.  In cursor form the launch advances the cursor by one."""
+    their softmax.  In cursor form the launch advances the cursor by one.
+
+    ``sel`` / ``count`` (with ``cursor``): row ``r`` goes to row ``sel[cursor * B + r]`` while ``cursor * B + r <
+    count``; the rows beyond are skipped."""
     _check(probs, torch.float32)
     if (idx is None) == (cursor is None):
         raise ValueError("exactly one of idx / cursor")
@@ -782,8 +811,71 @@ def window_probs(src: torch.Tensor, probs: torch.Tensor, idx: Optional[torch.Ten
         raise ValueError("idx must hold B window numbers")
     d.update({"idx": ptr(idx), "cursor": ptr(cursor), "lo": lo, "hi": N if hi is None else hi, "probs": ptr(probs),
               "nprobs": N})
-    lib().window_probs(stream(), d)
+    s = selection_args(sel, count, idx, cursor)
+    if s:
+        d.update(s)
+        lib().window_probs_sel(stream(), d)
+    else:
+        lib().window_probs(stream(), d)
     return probs
+
+
+def window_power(rec: torch.Tensor, fs, ts, window: Tuple[int, int]) -> torch.Tensor:
+    """The power of every window of a resident recording ``rec`` [C, F, T] (fp32): fp32 [len(fs) * len(ts)],
+    ``power[a * len(ts) + b]`` = the mean over the channels of the mean over the window at ``(fs[a], ts[b])`` of
+    ``(x - the window's own mean in that channel)^2`` -- :func:`sample_power`'s definition applied to a window
+    (inference.window_power_reference; two passes with fp64 accumulators, a fixed reduction order)."""
+    _check(rec, torch.float32)
+    if rec.dim() != 3:
+        raise ValueError("recording must be [C, F, T]")
+    C, Fn, Tn = rec.shape
+    fs, ts = _starts(fs, rec.device), _starts(ts, rec.device)
+    power = torch.empty(fs.numel() * ts.numel(), device=rec.device, dtype=torch.float32)
+    lib().window_power(stream(), {"rec": ptr(rec), "fs": ptr(fs), "ts": ptr(ts), "power": ptr(power), "C": C,
+                                  "F": Fn, "T": Tn, "nf": fs.numel(), "nt": ts.numel(), "Wf": window[0],
+                                  "Wt": window[1]})
+    return power
+
+
+def gate_ratio(gate_db: float) -> float:
+    """``10^(gate_db / 10)`` rounded to fp32 once on the host: the factor on the noise floor above which a window's
+    power makes it active."""
+    import numpy as np
+    return float(np.float32(10.0 ** (float(gate_db) / 10.0)))
+
+
+def select_windows(power: torch.Tensor, floor: torch.Tensor, gate_db: float, nt: int, lo: int = 0,
+                   hi: Optional[int] = None, sel: Optional[torch.Tensor] = None,
+                   count: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None):
+    """The active windows of ``[lo, hi)``: window ``n`` is active iff ``not (power[n] < floor[n // nt] * ratio)`` with
+    ``ratio`` = :func:`gate_ratio` and one fp32 multiply, so a NaN power is active.  ``power``: fp32 [N] on the
+    device; ``floor``: fp32, one noise floor per fiber start.  Returns ``(sel, count, active)``: ``sel`` int64 (at
+    least ``hi - lo`` entries) whose first ``count`` entries are the active window numbers in ascending order -- the
+    rest is left as it was, -1 in a buffer allocated here; ``count`` a device int64 scalar; ``active`` uint8 [N],
+    zero outside ``[lo, hi)``.  Buffers passed in are written in place.  The order is that of the window numbers on
+    every run (block counts, a scan, a ranked scatter; no atomics)."""
+    _check(power, torch.float32)
+    _check(floor, torch.float32)
+    N = power.numel()
+    hi = N if hi is None else hi
+    dev = power.device
+    if sel is None:
+        sel = torch.full((max(hi - lo, 1),), -1, dtype=torch.int64, device=dev)
+    if count is None:
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+    if active is None:
+        active = torch.empty(N, dtype=torch.uint8, device=dev)
+    _check(sel, torch.int64)
+    _check(count, torch.int64)
+    _check(active, torch.uint8)
+    if active.numel() != N or count.numel() != 1:
+        raise ValueError("active must hold one flag per window and count one number")
+    offs = torch.empty(lib().select_blocks(N), dtype=torch.int64, device=dev)
+    lib().select_windows(stream(), {"power": ptr(power), "floor": ptr(floor), "ratio": gate_ratio(gate_db), "N": N,
+                                    "lo": int(lo), "hi": int(hi), "nfloor": floor.numel(), "nt": int(nt),
+                                    "active": ptr(active), "sel": ptr(sel), "cap": sel.numel(), "offs": ptr(offs),
+                                    "noffs": offs.numel(), "count": ptr(count)})
+    return sel, count, active
 
 
 def window_cell_weights(starts, win: int, length: int, cell: int):
