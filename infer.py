@@ -6,6 +6,8 @@
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 infer.py ...   # windows sharded over ranks
     python infer.py ... --chunk 2000 [--ring 4096]   # read and evaluate the recording 2000 time samples at a time
     python infer.py ... --gate_db 3 [--noise_floor auto|P]   # evaluate only windows 3 dB above the noise floor
+    python infer.py ... --chunk 2000 --gate_db 3 --noise_floor running [--floor_history 64]   # the gate on the chunked
+        # run: the floor is the running median of the last 64 time indices (or --noise_floor P, a fixed power)
 """
 import argparse
 import os
@@ -36,18 +38,32 @@ def main():
                          "evaluated, the others are reported as quiet (pred -1); default: no gate")
     ap.add_argument("--noise_floor", default="auto",
                     help="with --gate_db: 'auto' (per fiber position, the lower median of its windows' powers over "
-                         "time) or a power")
+                         "time; not with --chunk), 'running' (with --chunk: the lower median of the last "
+                         "--floor_history time indices, the window's own included) or a power")
+    ap.add_argument("--floor_history", type=int, default=64,
+                    help="with --noise_floor running: time indices the running median looks back over")
+    ap.add_argument("--floor_warmup", type=int, default=None,
+                    help="with --noise_floor running: every window is active until this many time indices exist "
+                         "(default: 8, at most --floor_history)")
     args = ap.parse_args()
-    if args.gate_db is not None and args.chunk is not None:
-        ap.error("--gate_db cannot be combined with --chunk: a growing recording has no activity gate")
     noise_floor = args.noise_floor
-    if noise_floor != "auto":
+    if args.gate_db is not None and args.chunk is not None and noise_floor == "auto":
+        ap.error("--gate_db with --chunk needs --noise_floor running (or a power): 'auto' is the median over the "
+                 "whole recording, which a growing one does not have")
+    if noise_floor == "running":
+        if args.chunk is None:
+            ap.error("--noise_floor running is the floor of a growing recording: it needs --chunk")
+        if args.floor_warmup is None:
+            args.floor_warmup = min(8, args.floor_history)
+        if not 1 <= args.floor_warmup <= args.floor_history <= 1024:
+            ap.error("1 <= --floor_warmup <= --floor_history <= 1024")
+    if noise_floor not in ("auto", "running"):
         try:
             noise_floor = float(noise_floor)
         except ValueError:
-            ap.error("--noise_floor must be 'auto' or a power")
-        if args.gate_db is None:
-            ap.error("--noise_floor needs --gate_db")
+            ap.error("--noise_floor must be 'auto', 'running' or a power")
+    if noise_floor != "auto" and args.gate_db is None:
+        ap.error("--noise_floor needs --gate_db")
 
     from mtl_das_pytorch_amd import use_engine_graph_queues
     use_engine_graph_queues()  # before the first HIP call
@@ -77,7 +93,7 @@ def main():
             rec = np.asarray(load_mat(args.recording, (args.key,)), dtype=np.float32)
         else:
             rec = np.load(args.recording, mmap_mode="r", allow_pickle=False)
-        res, live_maps = live_run(model, args, rec, stride, cell if args.map else None, ctx, use_engine)
+        res, live_maps = live_run(model, args, rec, stride, cell if args.map else None, ctx, use_engine, noise_floor)
     else:
         if args.recording.endswith(".mat"):
             rec = np.asarray(load_mat(args.recording, (args.key,)), dtype=np.float32)
@@ -112,16 +128,19 @@ def main():
     shutdown(ctx)
 
 
-def live_run(model, args, rec, stride, cell, ctx, use_engine):
+def live_run(model, args, rec, stride, cell, ctx, use_engine, noise_floor="running"):
     """The recording through a LiveRecording, ``--chunk`` time samples at a time: the result dict of
-    predict_recording (windows in its order) and, with ``cell``, the maps of prediction_map."""
+    predict_recording (windows in its order) and, with ``cell``, the maps of prediction_map.  With ``--gate_db`` the
+    live gate at ``noise_floor`` ("running" or a power)."""
     import numpy as np
     from mtl_das_pytorch_amd.inference import WINDOW, LiveRecording
     rec3 = rec if rec.ndim == 3 else rec[None]
     C, F, T = rec3.shape
     ring = args.ring if args.ring is not None else max(8 * WINDOW[1], WINDOW[1] + min(args.chunk, 1 << 14))
     live = LiveRecording(model, args.model, F, C=C, stride=stride, cell=cell, ring=ring, batch=args.batch_size,
-                         ctx=ctx, use_engine=use_engine)
+                         ctx=ctx, use_engine=use_engine, gate_db=args.gate_db,
+                         noise_floor=noise_floor if args.gate_db is not None else "running",
+                         floor_history=args.floor_history, floor_warmup=args.floor_warmup or 1)
     outs = []
     for t in range(0, T, args.chunk):
         outs.append(live.push(np.ascontiguousarray(rec3[:, :, t:t + args.chunk], dtype=np.float32)))

@@ -511,6 +511,43 @@ void live_map(int64_t stream, py::dict d, std::vector<int> fs, std::vector<int64
   check(launch_live_map(a, I(d, "nrows"), fs.data(), jlo.data(), jn.data(), S(stream)), "live_map");
 }
 
+// the live gate's dicts: the live fields, the rings and the selection, each where the launch needs it (0 otherwise)
+LiveGateArgs parse_live_gate(const py::dict& d) {
+  LiveGateArgs a{};
+  a.live = parse_live(d);
+  a.power = P<float>(d, "power"); a.floor = P<float>(d, "floor"); a.active = P<uint8_t>(d, "active");
+  a.sel = P<int64_t>(d, "sel"); a.cap = I(d, "cap"); a.cursor = P<int64_t>(d, "cursor");
+  a.count = P<int64_t>(d, "count");
+  a.Jcap = (int)I(d, "Jcap"); a.n0 = I(d, "n0"); a.n1 = I(d, "n1");
+  return a;
+}
+
+void ring_window_power(int64_t stream, py::dict d) {
+  check(launch_ring_window_power(parse_live_gate(d), S(stream)), "ring_window_power");
+}
+
+void running_floor(int64_t stream, py::dict d) {
+  check(launch_running_floor(parse_live_gate(d), (int)I(d, "history"), (int)I(d, "warmup"), S(stream)),
+        "running_floor");
+}
+
+void live_select(int64_t stream, py::dict d) {
+  check(launch_live_select(parse_live_gate(d), (float)F(d, "ratio"), P<float>(d, "table"), I(d, "nrows"),
+                           (int)I(d, "pitch"), P<int64_t>(d, "offs"), I(d, "noffs"), S(stream)), "live_select");
+}
+
+void gather_windows_ring_sel(int64_t stream, py::dict d) {
+  check(launch_gather_windows_ring_sel(parse_live_gate(d), P<bf16_t>(d, "out"), P<int64_t>(d, "lab_out"),
+                                       (int)I(d, "lab_w"), S(stream)), "gather_windows_ring_sel");
+}
+
+void live_probs_sel(int64_t stream, py::dict d) {
+  const std::vector<int> ncls = parse_ncls(d, "live_probs_sel");
+  check(launch_live_probs_sel(parse_live_gate(d), P<const float>(d, "src"), (int)I(d, "softmax"), (int)ncls.size(),
+                              ncls.data(), (int)I(d, "K"), P<float>(d, "table"), I(d, "nrows"), (int)I(d, "pitch"),
+                              S(stream)), "live_probs_sel");
+}
+
 void pool3(int is_max, int backward, int64_t stream, py::dict d) {
   PoolArgs a{};
   a.x = P<const bf16_t>(d, "x"); a.ldx = (int)I(d, "ldx");
@@ -651,7 +688,12 @@ PYBIND11_MODULE(_mda_hip, m) {
   m.def("ring_append", &ring_append);
   m.def("gather_windows_ring", &gather_windows_ring);
   m.def("live_probs", &live_probs);
-  m.def("live_map", &live_map, py::arg("stream"), py::arg("d"), py::arg("fs"), py::arg("jlo"), py::arg("jn"));
+  m.def("ring_window_power", &ring_window_power);
+  m.def("running_floor", &running_floor);
+  m.def("live_select", &live_select);
+  m.def("gather_windows_ring_sel", &gather_windows_ring_sel);
+  m.def("live_probs_sel", &live_probs_sel);
+  m.def("live_map", &live_map,py::arg("stream"), py::arg("d"), py::arg("fs"), py::arg("jlo"), py::arg("jn"));
   m.def("wgrad_table", &wgrad_table);
   m.def("wgrad_batched", &wgrad_batched, py::arg("cfg"), py::arg("table"), py::arg("nj"), py::arg("nblocks"),
         py::arg("stream"), py::arg("cap") = 0);

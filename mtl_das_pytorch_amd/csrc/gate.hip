@@ -20,24 +20,20 @@ namespace mda {
 
 namespace {
 
-// the 256 partial sums in a fixed tree order; every thread returns the total
-DEV double block_sum(double v, double* s_red) {
-  __syncthreads();  // (the previous sum's readers)
-  s_red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) s_red[threadIdx.x] += s_red[threadIdx.x + o];
-    __syncthreads();
-  }
-  return s_red[0];
-}
+// the resident recording [C][F][T] as the source of window_power_body: time t is column t
+struct LinearSource {
+  const float* rec;
+  int T;
+  DEV int64_t column(int t) const { return t; }
+  DEV const float* base() const { return rec; }
+  DEV int64_t pitch() const { return T; }
+};
 
 // One block per window, grid-stride over the windows; element e of a window's plane is (e / Wt, e % Wt), threads
 // along time.  A window that does not lie inside the recording has no power: NaN, which the selection keeps.
 __global__ __launch_bounds__(256) void window_power_kernel(PowerArgs a) {
   __shared__ double s_red[256];
-  const int HW = a.Wf * a.Wt;
-  const int64_t N = (int64_t)a.nf * a.nt, plane = (int64_t)a.F * a.T;
+  const int64_t N = (int64_t)a.nf * a.nt;
   for (int64_t n = blockIdx.x; n < N; n += gridDim.x) {
     const int wa = (int)(n / a.nt), wb = (int)(n - (int64_t)wa * a.nt);
     const int f0 = a.fs[wa], t0 = a.ts[wb];
@@ -45,30 +41,9 @@ __global__ __launch_bounds__(256) void window_power_kernel(PowerArgs a) {
       if (threadIdx.x == 0) a.power[n] = __builtin_nanf("");
       continue;
     }
-    double total = 0.0;
-    for (int c = 0; c < a.C; ++c) {
-      const float* __restrict__ x = a.rec + c * plane + (int64_t)f0 * a.T + t0;
-      double acc = 0.0;
-      for (int e = threadIdx.x; e < HW; e += 256) {
-        const int h = e / a.Wt;
-        acc += (double)x[(int64_t)h * a.T + (e - h * a.Wt)];
-      }
-      const double mean = block_sum(acc, s_red) / (double)HW;
-      acc = 0.0;
-      for (int e = threadIdx.x; e < HW; e += 256) {
-        const int h = e / a.Wt;
-        const double d = (double)x[(int64_t)h * a.T + (e - h * a.Wt)] - mean;
-        acc += d * d;
-      }
-      total += block_sum(acc, s_red) / (double)HW;
-    }
-    if (threadIdx.x == 0) a.power[n] = (float)(total / (double)a.C);
+    const float p = window_power_body(LinearSource{a.rec, a.T}, a.C, a.F, a.Wf, a.Wt, f0, t0, s_red);
+    if (threadIdx.x == 0) a.power[n] = p;
   }
-}
-
-// lanes of the wave below this one whose bit is set in the ballot
-DEV int lanes_below(unsigned long long m) {
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
 
 // Block i owns windows 256 i .. 256 i + 255: their flags and how many are set.
@@ -80,34 +55,15 @@ __global__ __launch_bounds__(256) void select_flags_kernel(SelectArgs a) {
     on = n >= a.lo && n < a.hi && !(a.power[n] < a.floor[n / a.nt] * a.ratio);
     a.active[n] = on ? 1 : 0;
   }
-  const unsigned long long m = __ballot(on);
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) a.offs[blockIdx.x] = (int64_t)(s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3]);
+  const int set = block_flag_count(on, s_wave);
+  if (threadIdx.x == 0) a.offs[blockIdx.x] = (int64_t)set;
 }
 
-// One block: the block counts become their exclusive prefix sums (in place, 256 at a time with a carry), the total
-// becomes the count.
+// One block: select_scan_body (window_batch.h).
 __global__ __launch_bounds__(256) void select_scan_kernel(int64_t* __restrict__ offs, int64_t nblocks,
                                                           int64_t* __restrict__ count) {
   __shared__ int64_t s_sum[256];
-  int64_t carry = 0;
-  for (int64_t base = 0; base < nblocks; base += 256) {
-    const int64_t i = base + threadIdx.x;
-    const int64_t own = i < nblocks ? offs[i] : 0;
-    s_sum[threadIdx.x] = own;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {  // inclusive scan
-      const int64_t v = threadIdx.x >= o ? s_sum[threadIdx.x - o] : 0;
-      __syncthreads();
-      s_sum[threadIdx.x] += v;
-      __syncthreads();
-    }
-    if (i < nblocks) offs[i] = carry + s_sum[threadIdx.x] - own;
-    carry += s_sum[255];
-    __syncthreads();  // (s_sum[255] is read before the next round overwrites it)
-  }
-  if (threadIdx.x == 0) *count = carry;
+  select_scan_body(offs, nblocks, count, s_sum);
 }
 
 // Block i writes its active windows from sel[offs[i]] on: a window's place is the number of active windows before
@@ -117,14 +73,8 @@ __global__ __launch_bounds__(256) void select_scatter_kernel(SelectArgs a) {
   __shared__ int s_wave[4];
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const bool on = n < a.N && a.active[n] != 0;
-  const unsigned long long m = __ballot(on);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) s_wave[wave] = __popcll(m);
-  __syncthreads();
-  if (!on) return;
-  int64_t at = a.offs[blockIdx.x] + lanes_below(m);
-  for (int w = 0; w < wave; ++w) at += s_wave[w];
-  if (at < a.cap) a.sel[at] = n;  // (at < count <= hi - lo <= cap: the launcher checks the capacity)
+  const int64_t at = ranked_place(on, a.offs[blockIdx.x], s_wave);
+  if (on && at < a.cap) a.sel[at] = n;  // (at < count <= hi - lo <= cap: the launcher checks the capacity)
 }
 
 // The selection as a gather source: batch row b of replay cur is entry cur * B + b of sel, while that is below the

@@ -443,6 +443,37 @@ struct LiveMapArgs {
 // h_*: host copies of fs / jlo / jn, checked (fs covers [0, F); 1 <= jn <= min(mw, Jcap); jlo >= 0)
 int launch_live_map(const LiveMapArgs& a, int64_t nrows, const int* h_fs, const int64_t* h_jlo, const int* h_jn,
                     hipStream_t st);
+// live_gate.hip: the activity gate of a growing recording.  Three rings of Jcap time indices, row
+// (j mod Jcap) * nf + a like the probability table: the windows' powers, their noise floors (the causal running lower
+// median of the last `history` powers of the fiber start, 0 before `warmup` of them exist) and their flags.
+struct LiveGateArgs {
+  LiveArgs live;
+  float* power;        // [Jcap * nf]
+  float* floor;        // [Jcap * nf]
+  uint8_t* active;     // [Jcap * nf]
+  int64_t* sel;        // [cap]: the active window numbers of the last selected range, ascending
+  int64_t cap;
+  int64_t* cursor;     // device scalars of the selection: the batch cursor of its replays and its count; they live
+  int64_t* count;      // in a tensor of their own (live_state stays LIVE_NSTATE scalars)
+  int Jcap;
+  int64_t n0, n1;      // the window numbers of the launch: whole time indices, n0 = j0 * nf, n1 = j1 * nf
+};
+// power ring rows of windows [n0, n1) read through the ring (window_power's accumulation: the same bits)
+int launch_ring_window_power(const LiveGateArgs& a, hipStream_t st);
+// floor ring rows of [n0, n1) from the power ring; history in 1 .. 1024, 1 <= warmup <= history,
+// Jcap >= history - 1 + the time indices of the range
+int launch_running_floor(const LiveGateArgs& a, int history, int warmup, hipStream_t st);
+// flags of [n0, n1) (!(power < floor * ratio), as select_windows) into the active ring; their table rows
+// [Jcap * nf][pitch] zeroed; sel / count as select_windows; then cursor = 0 and LIVE_NEXT = n1.  offs: workspace of
+// select_blocks(n1 - n0) entries
+int launch_live_select(const LiveGateArgs& a, float ratio, float* table, int64_t nrows, int pitch, int64_t* offs,
+                       int64_t noffs, hipStream_t st);
+// gather_windows_ring with batch row r = window sel[cursor * B + r] while that entry is below count (padding beyond)
+int launch_gather_windows_ring_sel(const LiveGateArgs& a, bf16_t* out, int64_t* lab_out, int lab_w, hipStream_t st);
+// live_probs over the selection into a table [nrows >= Jcap * nf][pitch = K + 1]: columns 0 .. K - 1 the
+// probabilities, column K 1.0; then cursor += 1
+int launch_live_probs_sel(const LiveGateArgs& a, const float* src, int softmax, int T, const int* ncls, int K,
+                          float* table, int64_t nrows, int pitch, hipStream_t st);
 // synth.hip: on-device synthetic DAS samples (data/synthetic.py physical model, Philox noise)
 constexpr int SYNTH_NPARAM = 9;  // per sample: distance, event, x0, t0, jitter[4], snr_db
 struct SynthArgs {

@@ -43,11 +43,6 @@ __global__ void ring_advance_kernel(LiveArgs a, int n, int flush) {
   a.state[LIVE_AVAIL] = avail;
 }
 
-static bool live_args_ok(const LiveArgs& a) {
-  return a.state && a.ring && a.g.C >= 1 && a.g.F >= 1 && a.g.nf >= 1 && a.st >= 1 && a.g.Wt >= 1 &&
-         a.R >= (int64_t)a.g.Wt + 1;
-}
-
 int launch_ring_append(const LiveArgs& a, const float* chunk, int n, int flush, hipStream_t st) {
   if (!live_args_ok(a) || n < 0 || (n > 0 && !chunk) || (n == 0 && !flush) || n > a.R - a.g.Wt) return -2;
   if (n > 0) {
@@ -59,25 +54,7 @@ int launch_ring_append(const LiveArgs& a, const float* chunk, int n, int flush, 
   return (int)hipGetLastError();
 }
 
-// The ring as a gather source: batch row b is window next + b = (j, a) while that is below avail; it starts at
-// fiber row fs[a] and time j * st (tend for the end-aligned index); time t is column t mod R.
-struct RingSource {
-  using time_type = int64_t;
-  const LiveArgs& a;
-  const int64_t next, avail, jend, tend;
-  DEV bool window(int b, int& f0, int64_t& t0) const {
-    const int64_t n = next + b;
-    if (n < 0 || n >= avail) return false;
-    const int64_t wj = n / a.g.nf;
-    f0 = a.g.fs[(int)(n - wj * a.g.nf)];
-    t0 = wj == jend ? tend : wj * a.st;
-    return t0 >= 0;
-  }
-  DEV int64_t column(int64_t t) const { return t % a.R; }
-  DEV const float* base() const { return a.ring; }
-  DEV int64_t pitch() const { return a.R; }
-};
-
+// The ring as a gather source is window_batch.h's RingSource: batch row b is window next + b.
 __global__ __launch_bounds__(256) void gather_windows_ring_kernel(LiveArgs a, bf16_t* __restrict__ out,
                                                                   int64_t* __restrict__ lab_out, int lab_w) {
   const int64_t* s = a.state;

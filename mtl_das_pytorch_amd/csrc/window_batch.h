@@ -3,6 +3,9 @@
 //
 //   * the gather body: the NHWC-8 pixel loop with the stem's tap packing and the window-edge padding, a template
 //     over the source (where batch row b's window starts, which column holds time t, base pointer and row pitch);
+//   * the ring as a source (RingSource), the window power body (a template over the source, so the ring's powers
+//     have the bits of the linear recording's) and the ordered selection's count / scan / rank pieces, shared by
+//     the two activity gates (gate.hip, live_gate.hip);
 //   * the probability element: softmax of a logits row, or exp of the owning task's log-probability;
 //   * the fiber side of the maps: the windows covering a cell (bisection) and the weight-band lookup;
 //   * the launchers' common checks: the batch geometry, the ncls packing, "the starts cover the axis".
@@ -73,6 +76,126 @@ int launch_gather(Kernel kernel, const Args& a, bf16_t* out, int64_t* lab_out, i
   const int blocks = (int)std::min<int64_t>((M + 255) / 256, 65535);
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, a, out, lab_out, lab_w);
   return (int)hipGetLastError();
+}
+
+// The ring as a gather source (live.hip, live_gate.hip): window n = (j, a) exists while n is below avail; it starts at
+// fiber row fs[a] and time j * st (tend for the end-aligned index jend); time t is column t mod R.  Batch row b is
+// window next + b.
+struct RingSource {
+  using time_type = int64_t;
+  const LiveArgs& a;
+  const int64_t next, avail, jend, tend;
+  DEV bool numbered(int64_t n, int& f0, int64_t& t0) const {
+    if (n < 0 || n >= avail) return false;
+    const int64_t wj = n / a.g.nf;
+    f0 = a.g.fs[(int)(n - wj * a.g.nf)];
+    t0 = wj == jend ? tend : wj * a.st;
+    return t0 >= 0;
+  }
+  DEV bool window(int b, int& f0, int64_t& t0) const { return numbered(next + b, f0, t0); }
+  DEV int64_t column(int64_t t) const { return t % a.R; }
+  DEV const float* base() const { return a.ring; }
+  DEV int64_t pitch() const { return a.R; }
+};
+
+// what every launch over the ring requires of it
+inline bool live_args_ok(const LiveArgs& a) {
+  return a.state && a.ring && a.g.C >= 1 && a.g.F >= 1 && a.g.nf >= 1 && a.st >= 1 && a.g.Wt >= 1 &&
+         a.R >= (int64_t)a.g.Wt + 1;
+}
+
+// the 256 partial sums in a fixed tree order; every thread returns the total
+DEV double block_sum(double v, double* s_red) {
+  __syncthreads();  // (the previous sum's readers)
+  s_red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) s_red[threadIdx.x] += s_red[threadIdx.x + o];
+    __syncthreads();
+  }
+  return s_red[0];
+}
+
+// The power of the window at (f0, t0) of a source [C][F][pitch], by one block of 256 threads (s_red: 256 doubles of
+// LDS): (1 / C) sum_c mean over the window of (x - mu_c)^2, mu_c the window's own mean in channel c.  Two passes with
+// fp64 accumulators; element e of a plane is (e / Wt, e % Wt), threads along time; a fixed reduction order and one
+// fp32 rounding, so the result does not depend on where the source keeps time t (src.column).  Every thread
+// returns it.
+template <class Source, class Time>
+DEV float window_power_body(const Source& src, int C, int F, int Wf, int Wt, int f0, Time t0, double* s_red) {
+  const int HW = Wf * Wt;
+  const float* __restrict__ x = src.base();
+  const int64_t pitch = src.pitch(), plane = (int64_t)F * pitch;
+  double total = 0.0;
+  for (int c = 0; c < C; ++c) {
+    const float* __restrict__ xc = x + c * plane + (int64_t)f0 * pitch;
+    double acc = 0.0;
+    for (int e = threadIdx.x; e < HW; e += 256) {
+      const int h = e / Wt;
+      acc += (double)xc[(int64_t)h * pitch + src.column(t0 + (e - h * Wt))];
+    }
+    const double mean = block_sum(acc, s_red) / (double)HW;
+    acc = 0.0;
+    for (int e = threadIdx.x; e < HW; e += 256) {
+      const int h = e / Wt;
+      const double d = (double)xc[(int64_t)h * pitch + src.column(t0 + (e - h * Wt))] - mean;
+      acc += d * d;
+    }
+    total += block_sum(acc, s_red) / (double)HW;
+  }
+  return (float)(total / (double)C);
+}
+
+// The ordered selection's pieces (gate.hip select_windows, live_gate.hip live_select): blocks of 256 candidates
+// count their set flags, one block turns the counts into exclusive prefix sums, and a candidate's place is the
+// number of set flags before it.  No atomics, no block waits on another.
+
+// lanes of the wave below this one whose bit is set in the ballot
+DEV int lanes_below(unsigned long long m) {
+  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
+// the number of set flags of the block (every thread of the 256 calls it; s_wave: 4 ints of LDS); thread 0's value
+DEV int block_flag_count(bool on, int* s_wave) {
+  const unsigned long long m = __ballot(on);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = __popcll(m);
+  __syncthreads();
+  return s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+}
+
+// One block: the block counts become their exclusive prefix sums (in place, 256 at a time with a carry), the total
+// becomes the count.
+DEV void select_scan_body(int64_t* __restrict__ offs, int64_t nblocks, int64_t* __restrict__ count, int64_t* s_sum) {
+  int64_t carry = 0;
+  for (int64_t base = 0; base < nblocks; base += 256) {
+    const int64_t i = base + threadIdx.x;
+    const int64_t own = i < nblocks ? offs[i] : 0;
+    s_sum[threadIdx.x] = own;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {  // inclusive scan
+      const int64_t v = threadIdx.x >= o ? s_sum[threadIdx.x - o] : 0;
+      __syncthreads();
+      s_sum[threadIdx.x] += v;
+      __syncthreads();
+    }
+    if (i < nblocks) offs[i] = carry + s_sum[threadIdx.x] - own;
+    carry += s_sum[255];
+    __syncthreads();  // (s_sum[255] is read before the next round overwrites it)
+  }
+  if (threadIdx.x == 0) *count = carry;
+}
+
+// The place of this thread's candidate among the set flags: those of the blocks before (block_off), of the block's
+// waves before (the ballots' counts), of the wave's lanes below (mbcnt).  Every thread of the 256 calls it; the
+// value is meaningful where ``on``.
+DEV int64_t ranked_place(bool on, int64_t block_off, int* s_wave) {
+  const unsigned long long m = __ballot(on);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) s_wave[wave] = __popcll(m);
+  __syncthreads();
+  int64_t at = block_off + lanes_below(m);
+  for (int w = 0; w < wave; ++w) at += s_wave[w];
+  return at;
 }
 
 // Column c of batch row r of the probability table.  softmax = 0 (Models A/B): src is logp [T][B][16] and the

@@ -18,6 +18,7 @@ from .program import (COMM_STREAM, SPILL_STREAM, Launch, Phase, k_adam, k_step_i
 from .program import NoiseSpec, k_gather_noise, k_noise_advance
 from .program import k_gather_windows_ring, k_live_probs
 from .program import k_gather_windows_sel, k_window_probs_sel
+from .program import k_gather_windows_ring_sel, k_live_probs_sel
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID, SIGMUL, ADD_RELU, POOL_RELU = range(6)
 
@@ -495,15 +496,17 @@ class LoweredProgram:
             return [self.logp.shape[1]]
         return [16 if o == 0 else 2 for o in self.lab_off]
 
-    def _prob_fields(self, table) -> dict:
+    def _prob_fields(self, table, flag_column: bool = False) -> dict:
         """The source side of a probability launch -- the heads' log-probabilities or Model C's logits, for the
-        columns of :meth:`prob_classes` -- after checking that ``table`` has those columns."""
+        columns of :meth:`prob_classes` -- after checking that ``table`` has those columns (``flag_column``: and one
+        more, the gated live table's)."""
         ncls = self.prob_classes()
+        cols = sum(ncls) + int(flag_column)
         if (table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous() or not table.is_cuda
-                or table.shape[1] != sum(ncls)):
-            raise ValueError(f"probability table must be a contiguous fp32 [N, {sum(ncls)}] tensor on the device")
+                or table.shape[1] != cols):
+            raise ValueError(f"probability table must be a contiguous fp32 [N, {cols}] tensor on the device")
         softmax = self.logp.dim() == 2
-        d = {"B": self.B, "src": P(self.logp), "softmax": int(softmax), "K": table.shape[1]}
+        d = {"B": self.B, "src": P(self.logp), "softmax": int(softmax), "K": sum(ncls)}
         if not softmax:
             d["ncls"] = ncls
         return d
@@ -527,12 +530,26 @@ class LoweredProgram:
         ph.keep = (probs, idx, cursor, sel, count)
         return ph
 
-    def live_gather_phase(self, ring, fs, state, st: int) -> Phase:
+    def _live_selection(self, sel, count, cursor) -> dict:
+        """The launch fields of a gated live step, empty without a selection: ``sel`` (device int64 window numbers),
+        ``count`` and ``cursor`` (device int64 scalars; ops.functional.live_gate_state) come together."""
+        if sel is None and count is None and cursor is None:
+            return {}
+        if sel is None or count is None or cursor is None:
+            raise ValueError("a live selection is sel, count and cursor together")
+        self._device_vector(sel, torch.int64, "the selection")
+        self._device_vector(count, torch.int64, "the selection's count", 1)
+        self._device_vector(cursor, torch.int64, "the selection's cursor", 1)
+        return {"sel": P(sel), "cap": sel.numel(), "count": P(count), "cursor": P(cursor), "Jcap": 1}
+
+    def live_gather_phase(self, ring, fs, state, st: int, sel=None, count=None, cursor=None) -> Phase:
         """The batch gather of live inference: the batch's (H0, W0) windows are cut from the time ring ``ring``
         ([C, F, R] fp32 on the device, sample t at column t mod R) into the stem's input, labels zeroed.  Batch row
         ``r`` is window ``next + r`` = ``(j, a)`` -- fiber start ``fs[a]`` (int32 device table), time start
         ``j * st`` -- while that is below ``avail``; the other rows are zeros (``state``: the device scalars of
-        ops.functional.live_state, advanced by ring_append and live_probs_phase)."""
+        ops.functional.live_state, advanced by ring_append and live_probs_phase).  ``sel`` / ``count`` / ``cursor``
+        (together): a gated live step (csrc/live_gate.hip) -- row ``r`` is window ``sel[cursor * B + r]`` while that
+        entry is below ``count``, zeros beyond."""
         self._window_source(ring, "ring")
         self._device_vector(fs, torch.int32, "the fiber window-start table")
         if ring.shape[2] < self.W0 + 1:
@@ -540,22 +557,36 @@ class LoweredProgram:
         self._device_vector(state, torch.int64, "the live scalars (live_state)", LIVE_NSTATE)
         d = self._stem_fields(ring, fs)
         d.update({"ring": P(ring), "state": P(state), "R": ring.shape[2], "st": int(st)})
+        s = self._live_selection(sel, count, cursor)
+        d.update(s)
         ph = Phase("live_gather")
-        ph.add("gather_windows_ring", k_gather_windows_ring, d)
-        ph.keep = (ring, fs, state)  # the launch holds their device pointers
+        if s:
+            ph.add("gather_windows_ring_sel", k_gather_windows_ring_sel, d)
+        else:
+            ph.add("gather_windows_ring", k_gather_windows_ring, d)
+        ph.keep = (ring, fs, state, sel, count, cursor)  # the launch holds their device pointers
         return ph
 
-    def live_probs_phase(self, table, state, nf: int, jcap: int) -> Phase:
+    def live_probs_phase(self, table, state, nf: int, jcap: int, sel=None, count=None, cursor=None) -> Phase:
         """After ``fwd_eval``: the valid batch rows' probabilities into the ring table ``table`` [>= jcap * nf, K]
-        at row ``(j mod jcap) * nf + a``; the launch then advances ``next`` by the number of valid rows."""
-        d = self._prob_fields(table)
+        at row ``(j mod jcap) * nf + a``; the launch then advances ``next`` by the number of valid rows.  ``sel`` /
+        ``count`` / ``cursor``: the rows are numbered by the selection, as in :meth:`live_gather_phase`; the table
+        is the gated one, [>= jcap * nf, K + 1] with the "evaluated" column last, and the launch advances the
+        cursor by one."""
+        s = self._live_selection(sel, count, cursor)
+        d = self._prob_fields(table, flag_column=bool(s))
         if jcap < 1 or nf < 1 or table.shape[0] < jcap * nf:
             raise ValueError(f"a table of {table.shape[0]} rows is below jcap * nf = {jcap * nf}")
         self._device_vector(state, torch.int64, "the live scalars (live_state)", LIVE_NSTATE)
         d.update({"state": P(state), "nf": int(nf), "table": P(table), "nrows": table.shape[0], "Jcap": int(jcap)})
         ph = Phase("live_probs")
-        ph.add("live_probs", k_live_probs, d)
-        ph.keep = (table, state)
+        if s:
+            d.update(s)
+            d.update({"Jcap": int(jcap), "pitch": table.shape[1]})
+            ph.add("live_probs_sel", k_live_probs_sel, d)
+        else:
+            ph.add("live_probs", k_live_probs, d)
+        ph.keep = (table, state, sel, count, cursor)
         return ph
 
     def _wgfin_args(self, convs=None):

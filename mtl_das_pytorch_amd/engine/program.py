@@ -445,3 +445,14 @@ def k_gather_windows_ring(d, st):
 def k_live_probs(d, st):
     """The batch's probabilities into the live ring table; advances the window counter by the valid rows."""
     lib().live_probs(st, d)
+
+
+def k_gather_windows_ring_sel(d, st):
+    """The batch's windows cut from the time ring by a live selection (csrc/live_gate.hip)."""
+    lib().gather_windows_ring_sel(st, d)
+
+
+def k_live_probs_sel(d, st):
+    """The selected batch rows' probabilities and their "evaluated" column into the gated ring table; advances the
+    batch cursor."""
+    lib().live_probs_sel(st, d)

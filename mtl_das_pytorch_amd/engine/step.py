@@ -96,8 +96,9 @@ def _window_phases(p, s: InferSource):
 
 def _live_phases(p, s: InferSource):
     t, c = s.tensors, s.consts
-    return (p.live_gather_phase(t["ring"], t["fs"], t["state"], c["st"]),
-            p.live_probs_phase(t["table"], t["state"], t["fs"].numel(), c["jcap"]))
+    by = {k: t[k] for k in ("sel", "count", "cursor") if k in t}  # a gated source: rows numbered by the selection
+    return (p.live_gather_phase(t["ring"], t["fs"], t["state"], c["st"], **by),
+            p.live_probs_phase(t["table"], t["state"], t["fs"].numel(), c["jcap"], **by))
 
 
 class StepRunner:
@@ -419,15 +420,27 @@ class StepRunner:
         self._run("infer")
 
     def set_live_source(self, ring: torch.Tensor, fs: torch.Tensor, state: torch.Tensor, table: torch.Tensor,
-                        st: int, jcap: int):
+                        st: int, jcap: int, sel: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+                        cursor: Optional[torch.Tensor] = None):
         """Live inference on a growing recording: ``live_step()`` then evaluates windows ``next .. next + B - 1`` of
         the time ring ``ring`` [C, F, R] -- window ``n = j * nf + a`` at ``(fs[a], j * st)``, those from ``avail`` on
         as padding -- and writes their probabilities to rows ``(j mod jcap) * nf + a`` of ``table``; the step's last
         kernel advances ``next`` by the valid rows.  ``state``: the device scalars (ops.functional.live_state) that
         ring_append advances as data arrives.  The graph is captured once per source: pushes, the wrap of the ring
-        and the end of the stream only change device state."""
-        self._set_source("live", InferSource({"ring": ring, "fs": fs, "state": state, "table": table},
-                                             {"st": int(st), "jcap": int(jcap)}, ("state", "table"), _live_phases))
+        and the end of the stream only change device state.
+
+        ``sel`` / ``count`` / ``cursor`` (together): a gated live source (ops.functional.live_select) --
+        ``live_step()`` then evaluates the next ``B`` entries of ``sel`` below ``count``, both read on the device by
+        every replay, into the gated table [>= jcap * nf, K + 1], and advances ``cursor``: ceil(count / B) calls
+        cover the selection of a piece with the one captured graph.  The three tensors are part of the source."""
+        tensors = {"ring": ring, "fs": fs, "state": state, "table": table}
+        rollback = ("state", "table")
+        if not (sel is None and count is None and cursor is None):
+            if sel is None or count is None or cursor is None:
+                raise ValueError("a live selection is sel, count and cursor together")
+            tensors.update(sel=sel, count=count, cursor=cursor)
+            rollback += ("cursor",)
+        self._set_source("live", InferSource(tensors, {"st": int(st), "jcap": int(jcap)}, rollback, _live_phases))
 
     def clear_live_source(self):
         """Release the live source (its graph, and the runner's hold on the ring and the table)."""

@@ -21,7 +21,8 @@ floor by the gate are reported as quiet and only the others are evaluated.
 
 :class:`LiveRecording` serves a recording that is still growing: chunks of time samples go into a ring, the windows
 that became available are evaluated by replays of one graph, and map columns are returned as they become final
-(csrc/live.hip on the engine path, a host ring and the fp32 module elsewhere).
+(csrc/live.hip on the engine path, a host ring and the fp32 module elsewhere).  ``LiveRecording(gate_db=...)`` gates
+the stream too: its noise floor runs along with it (:func:`running_floor_reference`; csrc/live_gate.hip).
 """
 from __future__ import annotations
 
@@ -112,6 +113,38 @@ def active_reference(power: np.ndarray, nt: int, gate_db: float, noise_floor="au
     p = np.asarray(power, dtype=np.float64)
     thr = np.repeat(noise_floor_reference(p, nt, noise_floor), nt) * 10.0 ** (float(gate_db) / 10.0)
     return ~(p < thr)
+
+
+def running_floor_reference(power, nf: int, history: int, warmup: int) -> np.ndarray:
+    """The noise floor that runs along with a stream, fp64 [nj, nf], of the window powers ``power`` [nj * nf] in live
+    numbering (``n = j * nf + a``).  Causal: with ``lo = max(0, j - history + 1)`` and ``m = j - lo + 1``,
+
+        floor[j, a] = sorted(power[lo .. j, a])[(m - 1) // 2]
+
+    the lower median of the last ``m <= history`` powers of fiber start ``a``, row ``j`` itself included and no row
+    after it, NaN ordered last as ``np.sort`` does; 0 -- "no floor yet", under which every window is active -- while
+    ``m < warmup``.  This is the definition; csrc/live_gate.hip evaluates it on the device.
+
+    A trailing median follows a level that persists: an event longer than about ``history / 2`` time indices
+    becomes the floor and fades from the flags.  (A floor that freezes while windows are active would depend on the
+    flags it decides, and is not what this is.)"""
+    if history < 1 or not 1 <= warmup <= history:
+        raise ValueError(f"1 <= warmup <= history, got warmup {warmup}, history {history}")
+    p = np.asarray(power, dtype=np.float64).reshape(-1, nf)
+    floor = np.zeros_like(p)
+    for j in range(len(p)):
+        lo = max(0, j - history + 1)
+        m = j - lo + 1
+        if m >= warmup:
+            floor[j] = np.sort(p[lo:j + 1], 0)[(m - 1) // 2]
+    return floor
+
+
+def live_active_reference(power, floor, gate_db: float) -> np.ndarray:
+    """The live gate's flags in fp64, bool like ``power``: active unless the power is below its own floor times
+    ``10^(gate_db / 10)`` -- a floor of 0 and a NaN power are active (nothing is hidden before the floor exists)."""
+    p, f = np.asarray(power, dtype=np.float64), np.asarray(floor, dtype=np.float64)
+    return ~(p < f.reshape(p.shape) * 10.0 ** (float(gate_db) / 10.0))
 
 
 def _power_db(power: np.ndarray) -> np.ndarray:
@@ -396,17 +429,27 @@ def prediction_map(res_or_probs, fs, ts, shape: Tuple[int, int], cell: Tuple[int
         from .ops import functional as HF
         m = HF.window_map(table.float().contiguous(), fs, ts, shape, window, cell)
         if active is not None:
-            m[:-1] = torch.where(m[-1] > 0, m[:-1] / m[-1], torch.full_like(m[:-1], float("nan")))
+            m = _divide_by_activity(m)
         m = m.cpu().numpy().astype(np.float64)
     else:
         table = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table
         m = window_map_reference(table, fs, ts, shape, cell, window)
         if active is not None:
-            with np.errstate(divide="ignore", invalid="ignore"):
-                m[:-1] = np.where(m[-1] > 0, m[:-1] / m[-1], np.nan)
+            m = _divide_by_activity(m)
     if active is None:
         return _task_maps(m)
     return dict(_task_maps(m[:-1]), activity_map=m[-1])
+
+
+def _divide_by_activity(m):
+    """A map [K + 1, ..] whose last class is the flag column's (``sum w active``), a tensor or an array, in place:
+    the other classes become ``sum w p / sum w active``, NaN where the activity is 0."""
+    if isinstance(m, torch.Tensor):
+        m[:-1] = torch.where(m[-1] > 0, m[:-1] / m[-1], torch.full_like(m[:-1], float("nan")))
+    else:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            m[:-1] = np.where(m[-1] > 0, m[:-1] / m[-1], np.nan)
+    return m
 
 
 def _task_maps(m: np.ndarray) -> Dict:
@@ -479,7 +522,10 @@ class LiveBook:
     columns are final at a given total, how ``push`` splits a chunk, and how many rows of the ring table are alive.
     It mirrors the device's scalars (csrc/live.hip ring_advance_kernel) and never reads them."""
 
-    def __init__(self, Wt: int, st: int, ring: int, ct: Optional[int] = None, table_indices: Optional[int] = None):
+    def __init__(self, Wt: int, st: int, ring: int, ct: Optional[int] = None, table_indices: Optional[int] = None,
+                 history: Optional[int] = None):
+        """``history``: a gated recording's noise floor reads the powers of the last ``history`` time indices (the
+        power ring has the table's ``jcap`` indices): those count as needed too.  None: no gate."""
         if ring < Wt + 1:
             raise ValueError(f"a ring of {ring} time columns is below the window's {Wt} + 1")
         if st < 1 or (ct is not None and ct < 1):
@@ -487,6 +533,10 @@ class LiveBook:
         self.Wt, self.st, self.R, self.ct = int(Wt), int(st), int(ring), ct
         # a sub-chunk adds at most (R - Wt) // st + 1 indices; a non-final column reaches back (Wt + ct) // st + 2
         carried = (self.Wt + ct) // self.st + 2 if ct is not None else 0
+        if history is not None and history < 1:
+            raise ValueError("the floor's history must be positive")
+        self.history = None if history is None else int(history)
+        carried = max(carried, self.history - 1 if self.history else 0)
         self.jcap = int(table_indices) if table_indices is not None else (self.R - self.Wt) // self.st + 1 + carried
         if self.jcap < 1:
             raise ValueError("the table needs at least one time index")
@@ -503,10 +553,14 @@ class LiveBook:
         return (total - self.Wt) // self.ct if (self.ct is not None and total >= self.Wt) else 0
 
     def first_needed(self) -> int:
-        """The oldest time index whose table rows a column not yet emitted still reads."""
-        if self.ct is None:
-            return self.j_done
-        return min(self.j_done, max(0, (self.q_done * self.ct - self.Wt) // self.st + 1))
+        """The oldest time index whose rows are still read: the table's by a column not yet emitted, the power
+        ring's by the floor of the next index (``history - 1`` indices back)."""
+        first = self.j_done
+        if self.history:  # not clamped at 0: the floor launch asks for history - 1 + the new indices from the start
+            first = self.j_done - (self.history - 1)
+        if self.ct is not None:
+            first = min(first, max(0, (self.q_done * self.ct - self.Wt) // self.st + 1))
+        return first
 
     def split(self, n: int):
         """The sizes ``push`` appends a chunk of ``n`` samples in: at most R - Wt each, so the data of the oldest
@@ -520,8 +574,8 @@ class LiveBook:
     def _check_table(self, j1: int, oldest: int):
         if j1 - oldest > self.jcap:
             raise ValueError(f"the probability table holds {self.jcap} time indices, this push needs {j1 - oldest} "
-                             "(its own and those that non-final map columns still read): a smaller chunk, a larger "
-                             "ring or table_indices")
+                             "(its own, those that non-final map columns still read and those of the noise floor's "
+                             "history): a smaller chunk, a larger ring or table_indices")
 
     def check_push(self, n: int):
         """Raise before anything is written if a step of this push would overwrite live rows of the table."""
@@ -574,14 +628,33 @@ def _task_names(model, model_type: str):
     return names, [ncls[t] for t in names]
 
 
+def _live_gate(gate_db, noise_floor, history, warmup) -> Dict:
+    """The checked gate of a :class:`LiveRecording`: ``floor`` None is the running floor, a number the fixed one
+    (which has no history and no warm-up)."""
+    from .ops.functional import MAX_FLOOR_HISTORY
+    if isinstance(noise_floor, str):
+        if noise_floor != "running":
+            raise ValueError(f"noise_floor must be \"running\" or a power, got {noise_floor!r}: \"auto\" is the median "
+                             "over a whole recording, and a stream has no end")
+        history, warmup = int(history), int(warmup)
+        if not 1 <= warmup <= history <= MAX_FLOOR_HISTORY:
+            raise ValueError(f"1 <= floor_warmup <= floor_history <= {MAX_FLOOR_HISTORY}, got floor_warmup {warmup}, "
+                             f"floor_history {history}")
+        return {"gate_db": float(gate_db), "floor": None, "history": history, "warmup": warmup}
+    return {"gate_db": float(gate_db), "floor": float(noise_floor), "history": 1, "warmup": 1}
+
+
 class _TorchLive:
     """The torch backend of :class:`LiveRecording`: a host (or ``device``) ring and table, the module in fp32."""
 
-    def __init__(self, model, model_type, C, F, R, fs, window, st, jcap, K, batch, device):
+    def __init__(self, model, model_type, C, F, R, fs, window, st, jcap, K, batch, device, gate=None):
         self.model, self.model_type, self.batch, self.device = model.eval().to(device), model_type, batch, device
         self.fs, self.window, self.st, self.jcap, self.R = fs, window, st, jcap, R
         self.ring = torch.full((C, F, R), float("nan"))
-        self.table = np.full((jcap * len(fs), K), np.nan, dtype=np.float32)
+        # gated: one more column, 1 for an evaluated window (the rows of quiet windows are zero)
+        self.gate, self.K = gate, K
+        self.table = np.full((jcap * len(fs), K + (gate is not None)), np.nan, dtype=np.float32)
+        self.recent = np.zeros((0, len(fs)))  # fp64 powers of the last history - 1 time indices
         self.total = 0
 
     def append(self, chunk: torch.Tensor):
@@ -593,45 +666,73 @@ class _TorchLive:
     def flush(self):
         pass
 
-    def evaluate(self, starts) -> np.ndarray:
-        """``starts``: [(j, t0)].  Evaluates the windows (j, a) in number order; returns their rows [m * nf, K]."""
+    def _flags(self, starts):
+        """The gate of the new windows by the fp64 references: (active, power, floor), each [m * nf] in number
+        order.  Powers from :func:`window_power_reference` on the ring's columns, floors from
+        :func:`running_floor_reference` over the carried powers and the new ones."""
+        nf, Wt = len(self.fs), self.window[1]
+        power = np.stack([window_power_reference(self.ring[:, :, (t0 + torch.arange(Wt)) % self.R], self.fs, [0],
+                                                 self.window) for _, t0 in starts])
+        g = self.gate
+        if g["floor"] is None:
+            k = len(self.recent)  # min(j0, history - 1) rows: the reference's rows from k on are the whole stream's
+            tail = np.concatenate([self.recent, power])
+            floor = running_floor_reference(tail.reshape(-1), nf, g["history"], g["warmup"])[k:]
+            self.recent = tail[max(0, len(tail) - (g["history"] - 1)):] if g["history"] > 1 else self.recent
+        else:
+            floor = np.full(power.shape, float(g["floor"]))
+        return live_active_reference(power, floor, g["gate_db"]).reshape(-1), power.reshape(-1), floor.reshape(-1)
+
+    def evaluate(self, starts):
+        """``starts``: [(j, t0)].  Evaluates the windows (j, a) in number order; returns their rows [m * nf, K] and
+        None -- gated: only the active ones go through the module, the rows are [m * nf, K + 1] (quiet: zero) and
+        come with the flags ``(active, power, floor)``."""
         nf, (Wf, Wt) = len(self.fs), self.window
         if not starts:
-            return np.zeros((0, self.table.shape[1]), dtype=np.float32)
+            return np.zeros((0, self.table.shape[1]), dtype=np.float32), None
+        flags = self._flags(starts) if self.gate is not None else None
         tiles = []
-        for j, t0 in starts:
+        for k, (j, t0) in enumerate(starts):
             cols = (t0 + torch.arange(Wt)) % self.R
-            for f0 in self.fs:
-                tiles.append(self.ring[:, int(f0):int(f0) + Wf][:, :, cols])
-        x = torch.stack(tiles)
+            for a, f0 in enumerate(self.fs):
+                if flags is None or flags[0][k * nf + a]:
+                    tiles.append(self.ring[:, int(f0):int(f0) + Wf][:, :, cols])
         rows = []
-        for i in range(0, len(x), self.batch):
-            ps = _torch_probs(self.model, self.model_type, x[i:i + self.batch].to(self.device))
+        for i in range(0, len(tiles), self.batch):
+            ps = _torch_probs(self.model, self.model_type, torch.stack(tiles[i:i + self.batch]).to(self.device))
             rows.append(torch.cat([p.float() for p in ps], 1).cpu())
-        rows = torch.cat(rows).numpy()
+        rows = torch.cat(rows).numpy() if rows else np.zeros((0, self.K), dtype=np.float32)
+        if flags is not None:
+            full = np.zeros((len(starts) * nf, self.K + 1), dtype=np.float32)
+            full[flags[0], :self.K] = rows
+            full[flags[0], self.K] = 1.0
+            rows = full
         for k, (j, _) in enumerate(starts):
             r = (j % self.jcap) * nf
             self.table[r:r + nf] = rows[k * nf:(k + 1) * nf]
-        return rows
+        return rows, flags
 
     def map_columns(self, wf: np.ndarray, cols) -> np.ndarray:
-        """fp64 [K, nfc, ncol]; ``wf``: fp64 [nf, nfc]; ``cols``: [(jlo, w)] per column."""
+        """fp64 [K, nfc, ncol]; ``wf``: fp64 [nf, nfc]; ``cols``: [(jlo, w)] per column.  Gated: [K + 1, ..], the
+        flag column's map last and the classes divided by it."""
         nf = len(self.fs)
         out = np.zeros((self.table.shape[1], wf.shape[1], len(cols)))
         for q, (jlo, w) in enumerate(cols):
             rows = [(j % self.jcap) * nf for j in range(jlo, jlo + len(w))]
             p = np.stack([self.table[r:r + nf] for r in rows]).astype(np.float64)  # [jn, nf, K]
             out[:, :, q] = np.einsum("ai,j,jak->ki", wf, w, p)
-        return out
+        return _divide_by_activity(out) if self.gate is not None else out
 
     def close(self):
         pass
 
 
 class _EngineLive:
-    """The engine backend: device ring, device scalars and ring table; one captured graph per live source."""
+    """The engine backend: device ring, device scalars and ring table; one captured graph per live source.  Gated
+    (csrc/live_gate.hip): rings of the windows' powers, floors and flags beside the table, which gains the
+    "evaluated" column; the graph's rows are numbered by the selection of the piece just appended."""
 
-    def __init__(self, model, model_type, C, F, R, fs, window, st, jcap, K, batch, device):
+    def __init__(self, model, model_type, C, F, R, fs, window, st, jcap, K, batch, device, gate=None):
         from .ops import functional as HF
         if window != WINDOW:
             raise ValueError(f"the lowered models take {WINDOW} windows")
@@ -641,13 +742,24 @@ class _EngineLive:
         dev = self.runner.p.device
         self.ring = torch.zeros(C, F, R, device=dev)
         self.state = HF.live_state(dev)
-        self.table = torch.zeros(jcap * len(fs), K, device=dev)
+        self.gate, self.K = gate, K
+        self.table = torch.zeros(jcap * len(fs), K + (gate is not None), device=dev)
         self.fs_d = HF._starts(fs, dev)
+        by = {}
+        if gate is not None:
+            n = jcap * len(fs)
+            self.power = torch.full((n,), float("nan"), device=dev)
+            # a fixed floor fills its ring once and running_floor is never launched
+            self.floor = torch.full((n,), float(gate["floor"]) if gate["floor"] is not None else 0.0, device=dev)
+            self.active = torch.zeros(n, dtype=torch.uint8, device=dev)
+            self.sel = torch.full((n,), -1, dtype=torch.int64, device=dev)  # a piece adds at most jcap indices
+            self.cursor, self.count = HF.live_gate_state(dev)
+            by = {"sel": self.sel, "count": self.count, "cursor": self.cursor}
         # one pinned staging buffer and its device twin, reused by every push
         self.stage_h = torch.empty(C * F * (R - window[1]), dtype=torch.float32).pin_memory()
         self.stage_d = torch.empty(C * F * (R - window[1]), dtype=torch.float32, device=dev)
         self.staged = None  # event: the last upload from stage_h has finished
-        self.runner.set_live_source(self.ring, self.fs_d, self.state, self.table, st, jcap)
+        self.runner.set_live_source(self.ring, self.fs_d, self.state, self.table, st, jcap, **by)
         self.runner.prepare_live()  # the one capture
 
     def append(self, chunk: torch.Tensor):
@@ -668,21 +780,38 @@ class _EngineLive:
     def flush(self):
         self.HF.ring_append(self.ring, self.state, None, len(self.fs), self.st, self.window[1], flush=True)
 
-    def evaluate(self, starts) -> np.ndarray:
-        nf = len(self.fs)
+    def evaluate(self, starts):
+        """As :meth:`_TorchLive.evaluate`.  Gated: power, floor and selection of the new windows are launched eagerly
+        (the range is the host's, LiveBook's), the count is read once (8 bytes) and the graph replayed
+        ceil(count / B) times."""
+        nf, HF = len(self.fs), self.HF
         m = len(starts) * nf
         if m == 0:
-            return np.zeros((0, self.table.shape[1]), dtype=np.float32)
+            return np.zeros((0, self.table.shape[1]), dtype=np.float32), None
+        if self.gate is not None:
+            g, (n0, n1) = self.gate, (starts[0][0] * nf, (starts[-1][0] + 1) * nf)
+            HF.ring_window_power(self.ring, self.state, self.fs_d, self.st, self.window, self.power, self.jcap, n0, n1)
+            if g["floor"] is None:
+                HF.running_floor(self.power, self.floor, nf, self.jcap, n0, n1, g["history"], g["warmup"])
+            HF.live_select(self.power, self.floor, self.active, self.table, self.state, self.sel, self.count,
+                           self.cursor, g["gate_db"], nf, self.jcap, n0, n1)
+            m = int(self.count.item())  # the one read-back
         for _ in range((m + self.B - 1) // self.B):
             self.runner.live_step()
         rows = torch.as_tensor([(j % self.jcap) * nf + a for j, _ in starts for a in range(nf)],
                                dtype=torch.int64).to(self.table.device)
-        return self.table.index_select(0, rows).cpu().numpy()
+        flags = None
+        if self.gate is not None:
+            flags = tuple(t.index_select(0, rows).cpu().numpy() for t in (self.active, self.power, self.floor))
+            flags = (flags[0].astype(bool),) + flags[1:]
+        return self.table.index_select(0, rows).cpu().numpy(), flags
 
     def map_columns(self, wf, cols) -> np.ndarray:
         F_ = self.ring.shape[1]
         m = self.HF.live_map(self.table, self.fs, F_, self.window[0], self.cf, self.jcap, [c[0] for c in cols],
                              [c[1] for c in cols])
+        if self.gate is not None:  # the flag column rode along as class K + 1: the division runs after the launch
+            m = _divide_by_activity(m)
         return m.cpu().numpy().astype(np.float64)
 
     def close(self):
@@ -711,14 +840,33 @@ class LiveRecording:
     counters and the table live on the device and every batch is one replay of one graph captured at construction
     (``captures`` stays at 1); the torch backend keeps a host ring and evaluates the module in fp32.
 
-    There is no activity gate here (``predict_recording(gate_db=...)``): every window is evaluated.  Gating a growing
-    recording needs a noise floor that runs along with the stream, which is a change of its own."""
+    ``gate_db``: the activity gate of :func:`predict_recording` on the growing recording -- a window is active unless
+    its power is below its noise floor times ``10^(gate_db / 10)``, and only active windows are evaluated.
+    ``noise_floor``: a power (one floor everywhere), or ``"running"``: per fiber start the lower median of the powers
+    of the last ``floor_history`` time indices, the window's own included (:func:`running_floor_reference`; causal, no
+    look-ahead), and no floor -- every window active -- before ``floor_warmup`` of them exist.  (``"auto"``, the
+    median over the whole recording, needs the stream's end and is refused.)  A trailing median follows a level that
+    persists: an event longer than about ``floor_history / 2`` time indices becomes the floor and fades from the
+    flags; a floor that freezes while windows are active would depend on its own flags and is not offered.  The
+    results gain ``active`` [m] bool, ``power_db`` [m] and ``floor_db`` [m] (-inf while warming up); a quiet window
+    has ``<task>_pred`` -1 and a zero ``<task>_prob`` row, and ``map_columns`` gains ``activity_map``
+    [nfc, ncols], its class maps being ``sum w p / sum w active`` (NaN where the activity is 0) as
+    ``prediction_map(active=...)``; ``class_map`` is that divided map.  With a fixed floor the calls together equal
+    ``predict_recording(rec, gate_db=..., noise_floor=P)`` and its map on the concatenated chunks.  On the engine
+    backend power, floor and the ordered selection of each appended piece run on the device (csrc/live_gate.hip), the
+    count of active windows is read back once per piece and the one graph replayed ceil(count / batch) times.  None:
+    no gate, every window evaluated."""
 
     def __init__(self, model: nn.Module, model_type: str, F: int, C: int = 1, stride=(100, 125), cell=None,
                  ring: int = 8 * WINDOW[1], batch: int = 32, device=None, use_engine: Optional[bool] = None,
-                 ctx: Optional[DistContext] = None, table_indices: Optional[int] = None, window=WINDOW):
+                 ctx: Optional[DistContext] = None, table_indices: Optional[int] = None, window=WINDOW,
+                 gate_db: Optional[float] = None, noise_floor="running", floor_history: int = 64,
+                 floor_warmup: int = 8):
         if ctx is not None and ctx.enabled and ctx.world > 1:
             raise ValueError("a live recording is not sharded: world > 1 is not supported")
+        self.gate = None
+        if gate_db is not None:
+            self.gate = _live_gate(gate_db, noise_floor, floor_history, floor_warmup)
         device = torch.device(device) if device is not None else (ctx.device if ctx else torch.device("cpu"))
         if use_engine is None:
             use_engine = device.type == "cuda"
@@ -727,7 +875,7 @@ class LiveRecording:
         self.cell = None if cell is None else (int(cell[0]), int(cell[1]))
         self.fs = window_starts(self.F, self.window[0], self.stride[0])
         self.book = LiveBook(self.window[1], self.stride[1], int(ring), None if cell is None else self.cell[1],
-                             table_indices)
+                             table_indices, history=None if self.gate is None else self.gate["history"])
         self.names, self.ncls = _task_names(model, model_type)
         K = sum(self.ncls)
         if self.cell is not None:
@@ -738,7 +886,7 @@ class LiveRecording:
             self.wf = window_cell_weights(self.fs, self.window[0], self.F, self.cell[0])  # raises if rows uncovered
         backend = _EngineLive if use_engine else _TorchLive
         self.backend = backend(model, model_type, self.C, self.F, int(ring), self.fs, self.window, self.stride[1],
-                               self.book.jcap, K, batch, device)
+                               self.book.jcap, K, batch, device, **({} if self.gate is None else {"gate": self.gate}))
         self.backend.cf = self.cell[0] if self.cell is not None else None
 
     @property
@@ -751,18 +899,32 @@ class LiveRecording:
         r = getattr(self.backend, "runner", None)
         return r.captures if r is not None else 0
 
-    def _result(self, rows, starts, q_first: int, maps) -> Dict:
-        """``rows``: the new windows' table rows per step; ``maps``: the class maps of the steps' new columns."""
+    def _result(self, evals, starts, q_first: int, maps) -> Dict:
+        """``evals``: per step the new windows' table rows and (gated) their flags; ``maps``: the class maps of the
+        steps' new columns."""
+        K, gated = sum(self.ncls), self.gate is not None
         pos = np.asarray([(int(f0), t0) for _, t0 in starts for f0 in self.fs], dtype=np.int64).reshape(-1, 2)
-        rows = np.concatenate(rows) if rows else np.zeros((0, sum(self.ncls)), dtype=np.float32)
-        probs = [p.contiguous() for p in torch.from_numpy(rows).split(self.ncls, 1)]
-        res = _result(self.model_type, self.names, probs, pos, None)
+        rows = np.concatenate([e[0] for e in evals]) if evals else np.zeros((0, K + gated), dtype=np.float32)
+        probs = [p.contiguous() for p in torch.from_numpy(rows[:, :K].copy()).split(self.ncls, 1)]
+        flags = None
+        if gated:
+            got = [e[1] for e in evals if e[1] is not None]
+            active, power, floor = (np.concatenate([g[i] for g in got]) if got else np.zeros(0, dtype=dt)
+                                    for i, dt in enumerate((bool, np.float64, np.float64)))
+            flags = (active, power)
+        res = _result(self.model_type, self.names, probs, pos, None, flags)
+        if gated:
+            res["floor_db"] = _power_db(floor)
         if self.cell is not None:
             maps = [m for m in maps if m is not None]
             nfc = -(-self.F // self.cell[0])
-            m = np.concatenate(maps, 2) if maps else np.zeros((sum(self.ncls), nfc, 0))
-            # class_map: every class of the table, before the tasks are marginalised
-            res["map_columns"] = dict(_task_maps(m), first=q_first, last=self.book.q_done, class_map=m)
+            m = np.concatenate(maps, 2) if maps else np.zeros((K + gated, nfc, 0))
+            # class_map: every class of the table, before the tasks are marginalised (gated: divided by the activity)
+            if gated:
+                res["map_columns"] = dict(_task_maps(m[:-1]), first=q_first, last=self.book.q_done, class_map=m[:-1],
+                                          activity_map=m[-1])
+            else:
+                res["map_columns"] = dict(_task_maps(m), first=q_first, last=self.book.q_done, class_map=m)
         return res
 
     def _emit(self, q0: int, q1: int, T: Optional[int]):

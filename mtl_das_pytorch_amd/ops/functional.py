@@ -1021,6 +1021,126 @@ def live_probs(src: torch.Tensor, table: torch.Tensor, state: torch.Tensor, nf: 
     return table
 
 
+# ---- the activity gate of a growing recording (csrc/live_gate.hip) ----------------------------------------------
+# Three rings of jcap time indices -- the windows' powers, their noise floors and their flags -- at row
+# (j mod jcap) * nf + a like the ring table, and a selection (sel, count, cursor) the captured step's rows are
+# numbered by.  Every launch works on the new window numbers [n0, n1): whole time indices, at most jcap of them.
+MAX_FLOOR_HISTORY = 1024  # running_floor keeps a column's trailing powers in LDS
+
+
+def live_gate_state(device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The device scalars of a live selection, ``(cursor, count)``: two int64 [1] views of one small tensor of their
+    own (:func:`live_state` keeps its LIVE_NSTATE scalars), both 0."""
+    s = torch.zeros(2, dtype=torch.int64, device=device)
+    return s[0:1], s[1:2]
+
+
+def _gate_rings(nf: int, jcap: int, n0: int, n1: int, **rings) -> dict:
+    """The range and the rings of a live gate launch, checked: ``rings`` by launch field name, each a contiguous
+    device vector of ``jcap * nf`` entries (``active``: uint8, the others fp32)."""
+    nf, jcap, n0, n1 = int(nf), int(jcap), int(n0), int(n1)
+    if nf < 1 or jcap < 1 or not 0 <= n0 <= n1 or n0 % nf or n1 % nf or (n1 - n0) // nf > jcap:
+        raise ValueError(f"windows [{n0}, {n1}) must be whole time indices of {nf} windows, at most jcap = {jcap}")
+    d = {"nf": nf, "Jcap": jcap, "n0": n0, "n1": n1}
+    for k, t in rings.items():
+        _check(t, torch.uint8 if k == "active" else torch.float32)
+        if t.dim() != 1 or t.numel() != jcap * nf:
+            raise ValueError(f"the {k} ring must hold jcap * nf = {jcap * nf} entries")
+        d[k] = ptr(t)
+    return d
+
+
+def _gate_selection(state: torch.Tensor, sel: torch.Tensor, count: torch.Tensor, cursor: torch.Tensor) -> dict:
+    for t in (state, sel, count, cursor):
+        _check(t, torch.int64)
+    if state.numel() != LIVE_NSTATE or count.numel() != 1 or cursor.numel() != 1 or sel.dim() != 1:
+        raise ValueError("state must be live_state, count / cursor one number each, sel an int64 vector")
+    return {"state": ptr(state), "sel": ptr(sel), "cap": sel.numel(), "count": ptr(count), "cursor": ptr(cursor)}
+
+
+def ring_window_power(ring: torch.Tensor, state: torch.Tensor, fs, st: int, window: Tuple[int, int],
+                      power: torch.Tensor, jcap: int, n0: int, n1: int) -> torch.Tensor:
+    """:func:`window_power` of the live windows ``[n0, n1)`` (``n = j * nf + a``, start ``(fs[a], j * st)``, ``tend``
+    for the end-aligned index) read from the time ring, into rows ``(j mod jcap) * nf + a`` of the power ring
+    ``power`` (fp32 [jcap * nf], in place).  The accumulation is :func:`window_power`'s, so the powers have the bits
+    of the linear recording's.  A window that is not available, or no longer in the ring, gets NaN."""
+    fs = _starts(fs, ring.device)
+    d = _live_args(ring, state, fs.numel(), st, window[1])
+    d.update(_gate_rings(fs.numel(), jcap, n0, n1, power=power))
+    d.update({"fs": ptr(fs), "Wf": window[0]})
+    lib().ring_window_power(stream(), d)
+    return power
+
+
+def running_floor(power: torch.Tensor, floor: torch.Tensor, nf: int, jcap: int, n0: int, n1: int, history: int,
+                  warmup: int) -> torch.Tensor:
+    """The causal noise floor of the live windows ``[n0, n1)`` into the floor ring (in place): for window ``(j, a)``
+    the lower median of the powers of fiber start ``a`` at the time indices ``max(0, j - history + 1) .. j`` (``m`` of
+    them, row ``j`` included), NaN ordered last; 0 while ``m < warmup`` (inference.running_floor_reference).  A
+    selection, so exact.  The power ring must still hold those indices: ``jcap >= history - 1 + (n1 - n0) / nf``."""
+    d = _gate_rings(nf, jcap, n0, n1, power=power, floor=floor)
+    if not 1 <= warmup <= history <= MAX_FLOOR_HISTORY:
+        raise ValueError(f"1 <= warmup <= history <= {MAX_FLOOR_HISTORY}, got warmup {warmup}, history {history}")
+    if jcap < history - 1 + (n1 - n0) // nf:
+        raise ValueError(f"rings of {jcap} time indices are below history - 1 + the range's {(n1 - n0) // nf}")
+    d.update({"history": int(history), "warmup": int(warmup)})
+    lib().running_floor(stream(), d)
+    return floor
+
+
+def live_select(power: torch.Tensor, floor: torch.Tensor, active: torch.Tensor, table: torch.Tensor,
+                state: torch.Tensor, sel: torch.Tensor, count: torch.Tensor, cursor: torch.Tensor, gate_db: float,
+                nf: int, jcap: int, n0: int, n1: int) -> None:
+    """The flags of the live windows ``[n0, n1)`` -- active iff ``not (power < floor * ratio)``, as
+    :func:`select_windows` -- into the active ring; ``sel[:count]`` becomes the active window numbers in ascending
+    order, the rest of ``sel`` is left as it was (``count`` / ``cursor``: :func:`live_gate_state`).  Every row of the range in the ring
+    table ``table`` [>= jcap * nf, K + 1] is zeroed (the rows are recycled).  The last launch sets the batch
+    cursor to 0 and ``state[LIVE_NEXT]`` to ``n1``."""
+    _check(table, torch.float32)
+    d = _gate_rings(nf, jcap, n0, n1, power=power, floor=floor, active=active)
+    d.update(_gate_selection(state, sel, count, cursor))
+    if table.dim() != 2 or table.shape[0] < jcap * nf:
+        raise ValueError(f"a table of {tuple(table.shape)} is below jcap * nf = {jcap * nf} rows")
+    if sel.numel() < n1 - n0:
+        raise ValueError(f"sel holds {sel.numel()} entries, the range {n1 - n0} windows")
+    offs = torch.empty(max(1, lib().select_blocks(n1 - n0)), dtype=torch.int64, device=power.device)
+    d.update({"ratio": gate_ratio(gate_db), "table": ptr(table), "nrows": table.shape[0], "pitch": table.shape[1],
+              "offs": ptr(offs), "noffs": offs.numel()})
+    lib().live_select(stream(), d)
+
+
+def gather_windows_ring_sel(ring: torch.Tensor, state: torch.Tensor, fs, st: int, window: Tuple[int, int], B: int,
+                            sel: torch.Tensor, count: torch.Tensor, cursor: torch.Tensor, taps: int = 0,
+                            off: int = 0, lab_w: int = 2):
+    """:func:`gather_windows_ring` with the batch rows numbered by a live selection: row ``r`` holds window
+    ``sel[cursor * B + r]`` while that entry is below ``count`` (:func:`live_gate_state`), zeros beyond."""
+    fs = _starts(fs, ring.device)
+    d = _live_args(ring, state, fs.numel(), st, window[1])
+    g, out, lab = _gather_out(ring.device, fs, window, B, taps, off, lab_w)
+    d.update(g)
+    d.update(_gate_selection(state, sel, count, cursor))
+    d["Jcap"] = 1  # (the gather touches no ring of the gate)
+    lib().gather_windows_ring_sel(stream(), d)
+    return out, lab
+
+
+def live_probs_sel(src: torch.Tensor, table: torch.Tensor, state: torch.Tensor, sel: torch.Tensor,
+                   count: torch.Tensor, cursor: torch.Tensor, nf: int, jcap: int, ncls: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """:func:`live_probs` over a live selection into the gated ring table ``table`` [>= jcap * nf, K + 1] (in place):
+    batch row ``r`` is window ``sel[cursor * B + r]`` = ``(j, a)`` while that entry is below the count and goes to row
+    ``(j mod jcap) * nf + a`` -- columns ``0 .. K - 1`` the probabilities, column ``K`` 1.0, "evaluated".  The launch
+    then advances the cursor by one."""
+    _check(table, torch.float32)
+    N, pitch = table.shape
+    if jcap < 1 or nf < 1 or N < jcap * nf:
+        raise ValueError(f"a table of {N} rows is below jcap * nf = {jcap * nf}")
+    _, d = _prob_source(src, pitch - 1, ncls)
+    d.update(_gate_selection(state, sel, count, cursor))
+    d.update({"nf": int(nf), "table": ptr(table), "nrows": N, "pitch": pitch, "Jcap": int(jcap)})
+    lib().live_probs_sel(stream(), d)
+    return table
+
+
 def live_map(table: torch.Tensor, fs, F: int, Wf: int, cf: int, jcap: int, jlo, wt) -> torch.Tensor:
     """Cell columns of the map from the ring table ``table`` [>= jcap * len(fs), K] -> [K, ceil(F / cf), ncol]
     (fp32).  Column ``q`` of the call is ``sum_a sum_j wf[a, i] wt[q][j] table[(j mod jcap) * nf + a]`` over the time
