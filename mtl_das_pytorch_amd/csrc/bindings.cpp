@@ -406,12 +406,18 @@ std::vector<int> parse_ncls(const py::dict& d, const char* what) {
   return ncls;
 }
 
+// the selection a gather / probability launch may be numbered by (absent: none)
+Selection parse_selection(const py::dict& d) {
+  return Selection{P<int64_t>(d, "sel"), P<int64_t>(d, "count"), I(d, "cap")};
+}
+
 WindowArgs parse_window(const py::dict& d) {
   WindowArgs a{};
   a.g = parse_geom(d);
   a.rec = P<const float>(d, "rec"); a.ts = P<const int>(d, "ts"); a.T = (int)I(d, "T"); a.nt = (int)I(d, "nt");
   a.idx = P<const int64_t>(d, "idx"); a.cursor = P<int64_t>(d, "cursor");
   a.lo = I(d, "lo"); a.hi = I(d, "hi");
+  a.s = parse_selection(d);
   return a;
 }
 
@@ -456,29 +462,11 @@ void select_windows(int64_t stream, py::dict d) {
   check(launch_select_windows(a, P<int64_t>(d, "count"), I(d, "noffs"), S(stream)), "select_windows");
 }
 
-WindowSelArgs parse_window_sel(const py::dict& d) {
-  WindowSelArgs a{};
-  static_cast<WindowArgs&>(a) = parse_window(d);
-  a.sel = P<const int64_t>(d, "sel"); a.count = P<const int64_t>(d, "count"); a.cap = I(d, "cap");
-  return a;
-}
-
-void gather_windows_sel(int64_t stream, py::dict d) {
-  check(launch_gather_windows_sel(parse_window_sel(d), P<bf16_t>(d, "out"), P<int64_t>(d, "lab_out"),
-                                  (int)I(d, "lab_w"), S(stream)), "gather_windows_sel");
-}
-
-void window_probs_sel(int64_t stream, py::dict d) {
-  const std::vector<int> ncls = parse_ncls(d, "window_probs_sel");
-  check(launch_window_probs_sel(parse_window_sel(d), P<const float>(d, "src"), (int)I(d, "softmax"),
-                                (int)ncls.size(), ncls.data(), (int)I(d, "K"), P<float>(d, "probs"), I(d, "nprobs"),
-                                S(stream)), "window_probs_sel");
-}
-
 LiveArgs parse_live(const py::dict& d) {
   LiveArgs a{};
   a.g = parse_geom(d);
   a.ring = P<float>(d, "ring"); a.state = P<int64_t>(d, "state"); a.R = (int)I(d, "R"); a.st = (int)I(d, "st");
+  a.s = parse_selection(d); a.cursor = P<int64_t>(d, "cursor");
   return a;
 }
 
@@ -495,8 +483,8 @@ void gather_windows_ring(int64_t stream, py::dict d) {
 void live_probs(int64_t stream, py::dict d) {
   const std::vector<int> ncls = parse_ncls(d, "live_probs");
   check(launch_live_probs(parse_live(d), P<const float>(d, "src"), (int)I(d, "softmax"), (int)ncls.size(),
-                          ncls.data(), (int)I(d, "K"), P<float>(d, "table"), I(d, "nrows"), (int)I(d, "Jcap"),
-                          S(stream)), "live_probs");
+                          ncls.data(), (int)I(d, "K"), P<float>(d, "table"), I(d, "nrows"), (int)I(d, "pitch"),
+                          (int)I(d, "Jcap"), S(stream)), "live_probs");
 }
 
 void live_map(int64_t stream, py::dict d, std::vector<int> fs, std::vector<int64_t> jlo, std::vector<int> jn) {
@@ -511,13 +499,11 @@ void live_map(int64_t stream, py::dict d, std::vector<int> fs, std::vector<int64
   check(launch_live_map(a, I(d, "nrows"), fs.data(), jlo.data(), jn.data(), S(stream)), "live_map");
 }
 
-// the live gate's dicts: the live fields, the rings and the selection, each where the launch needs it (0 otherwise)
+// the live gate's dicts: the live fields, the rings and the range, each where the launch needs it (0 otherwise)
 LiveGateArgs parse_live_gate(const py::dict& d) {
   LiveGateArgs a{};
   a.live = parse_live(d);
   a.power = P<float>(d, "power"); a.floor = P<float>(d, "floor"); a.active = P<uint8_t>(d, "active");
-  a.sel = P<int64_t>(d, "sel"); a.cap = I(d, "cap"); a.cursor = P<int64_t>(d, "cursor");
-  a.count = P<int64_t>(d, "count");
   a.Jcap = (int)I(d, "Jcap"); a.n0 = I(d, "n0"); a.n1 = I(d, "n1");
   return a;
 }
@@ -534,18 +520,6 @@ void running_floor(int64_t stream, py::dict d) {
 void live_select(int64_t stream, py::dict d) {
   check(launch_live_select(parse_live_gate(d), (float)F(d, "ratio"), P<float>(d, "table"), I(d, "nrows"),
                            (int)I(d, "pitch"), P<int64_t>(d, "offs"), I(d, "noffs"), S(stream)), "live_select");
-}
-
-void gather_windows_ring_sel(int64_t stream, py::dict d) {
-  check(launch_gather_windows_ring_sel(parse_live_gate(d), P<bf16_t>(d, "out"), P<int64_t>(d, "lab_out"),
-                                       (int)I(d, "lab_w"), S(stream)), "gather_windows_ring_sel");
-}
-
-void live_probs_sel(int64_t stream, py::dict d) {
-  const std::vector<int> ncls = parse_ncls(d, "live_probs_sel");
-  check(launch_live_probs_sel(parse_live_gate(d), P<const float>(d, "src"), (int)I(d, "softmax"), (int)ncls.size(),
-                              ncls.data(), (int)I(d, "K"), P<float>(d, "table"), I(d, "nrows"), (int)I(d, "pitch"),
-                              S(stream)), "live_probs_sel");
 }
 
 void pool3(int is_max, int backward, int64_t stream, py::dict d) {
@@ -683,16 +657,12 @@ PYBIND11_MODULE(_mda_hip, m) {
   m.def("window_power", &window_power);
   m.def("select_windows", &select_windows);
   m.def("select_blocks", &select_blocks);
-  m.def("gather_windows_sel", &gather_windows_sel);
-  m.def("window_probs_sel", &window_probs_sel);
   m.def("ring_append", &ring_append);
   m.def("gather_windows_ring", &gather_windows_ring);
   m.def("live_probs", &live_probs);
   m.def("ring_window_power", &ring_window_power);
   m.def("running_floor", &running_floor);
   m.def("live_select", &live_select);
-  m.def("gather_windows_ring_sel", &gather_windows_ring_sel);
-  m.def("live_probs_sel", &live_probs_sel);
   m.def("live_map", &live_map,py::arg("stream"), py::arg("d"), py::arg("fs"), py::arg("jlo"), py::arg("jn"));
   m.def("wgrad_table", &wgrad_table);
   m.def("wgrad_batched", &wgrad_batched, py::arg("cfg"), py::arg("table"), py::arg("nj"), py::arg("nblocks"),

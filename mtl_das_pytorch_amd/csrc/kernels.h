@@ -337,13 +337,22 @@ int launch_gather_batch_noise(const float* X, const int64_t* idx, const int64_t*
 int launch_noise_advance(int64_t* draw, hipStream_t st);
 int launch_pool3(int is_max, int backward, const PoolArgs& a, hipStream_t st);
 // window.hip / live.hip: sliding-window inference over a resident and over a growing recording.  What the two share
-// -- the batch geometry below, the gather body, the probability element, the fiber side of the maps and the
-// launchers' common checks -- is in window_batch.h.
+// -- the batch geometry and the selection below, the gather body, the selected numbering, the probability element,
+// the fiber side of the maps and the launchers' common checks -- is in window_batch.h.
 struct WindowGeom {
   const int* fs;      // window starts along the fiber [nf]
   int C, F, nf;       // channels and fiber rows of the source, fiber window count
   int B, Wf, Wt;      // batch rows, window size
   int taps, off;      // vertical tap packing of a 1-channel stem (gather_batch)
+};
+// The batch rows of a gather / probability launch numbered by an on-device selection (select_windows, live_select):
+// in replay cur of a batch cursor, row r holds window sel[cur * B + r] while cur * B + r < min(*count, cap), and is
+// padding beyond: gathered as zeros, skipped by the store, which advances the cursor by one.  sel and count come
+// together; both null: no selection.
+struct Selection {
+  int64_t* sel;       // [cap]: the active window numbers, ascending
+  int64_t* count;     // device scalar, read by every replay
+  int64_t cap;
 };
 // window.hip: windows cut on the device from a recording [C][F][T], probabilities into a resident table,
 // overlapping windows averaged into a cell map
@@ -352,11 +361,13 @@ struct WindowArgs {
   const float* rec;   // recording [C][F][T] fp32 (gather_windows only)
   const int* ts;      // window starts along time [nt]; window n = a * nt + b
   int T, nt;
-  // batch row r holds window idx[r], or lo + *cursor * B + r (exactly one of idx / cursor is set); a row whose
-  // window number is outside [lo, hi) is padding: gathered as zeros, skipped by window_probs
+  // batch row r holds window idx[r], or lo + *cursor * B + r (exactly one of idx / cursor is set), or the entry of
+  // the selection s (with the cursor); a row whose window number is outside [lo, hi) is padding: gathered as zeros,
+  // skipped by window_probs
   const int64_t* idx;
   int64_t* cursor;    // advanced by window_probs
   int64_t lo, hi;
+  Selection s;
 };
 int launch_gather_windows(const WindowArgs& a, bf16_t* out, int64_t* lab_out, int lab_w, hipStream_t st);
 // softmax = 0: src = logp [T][B][16], ncls[t] columns per task side by side (their sum is K); 1: src = logits [B][K]
@@ -376,8 +387,8 @@ struct MapArgs {
 };
 // h_fs / h_ts: host copies of the start tables, checked to cover [0, F) x [0, T) (-2 otherwise)
 int launch_window_map(const MapArgs& a, const int* h_fs, const int* h_ts, hipStream_t st);
-// gate.hip: the activity gate of resident-recording inference -- the windows' power, the ordered selection of the
-// active ones, and the gather / probability store numbered by that selection
+// gate.hip: the activity gate of resident-recording inference -- the windows' power and the ordered selection of the
+// active ones, which gather_windows / window_probs take as WindowArgs::s
 struct PowerArgs {
   const float* rec;   // recording [C][F][T] fp32
   const int* fs;      // window starts [nf], [nt]; window n = a * nt + b
@@ -400,17 +411,6 @@ struct SelectArgs {
 int64_t select_blocks(int64_t N);
 // three launches (flags + block counts, scan of the counts, ranked scatter); count: device int64, the active windows
 int launch_select_windows(const SelectArgs& a, int64_t* count, int64_t noffs, hipStream_t st);
-// WindowArgs in cursor form with the batch rows numbered by a selection: in replay *cursor, row r holds window
-// sel[*cursor * B + r] while *cursor * B + r < min(*count, cap), and is padding beyond (or where that window number
-// is outside [lo, hi)): gathered as zeros, skipped by the store, which advances the cursor
-struct WindowSelArgs : WindowArgs {
-  const int64_t* sel;
-  const int64_t* count;  // device scalar, read by every replay
-  int64_t cap;           // entries of sel
-};
-int launch_gather_windows_sel(const WindowSelArgs& a, bf16_t* out, int64_t* lab_out, int lab_w, hipStream_t st);
-int launch_window_probs_sel(const WindowSelArgs& a, const float* src, int softmax, int T, const int* ncls, int K,
-                            float* probs, int64_t nprobs, hipStream_t st);
 // live.hip: inference on a growing recording -- the time axis as a ring of R columns, windows numbered time-major
 // (n = j * nf + a: time index j starts at j * st), probabilities into a ring table, final map columns
 enum { LIVE_TOTAL = 0, LIVE_AVAIL, LIVE_NEXT, LIVE_JEND, LIVE_TEND, LIVE_NSTATE };
@@ -422,14 +422,20 @@ struct LiveArgs {
   // jend / tend = number and start of the end-aligned time index (jend = -1 until the stream is flushed)
   int64_t* state;
   int R, st;
+  // a gated step (live_gate.hip): the rows are numbered by the selection and its own batch cursor, a device scalar
+  // beside count (state stays LIVE_NSTATE scalars); s and cursor come together
+  Selection s;
+  int64_t* cursor;
 };
 // chunk [C][F][n] (n <= R - Wt) -> ring, total += n, avail from the new total; flush: the stream ends at the new
 // total (n may be 0) and the end-aligned index, if there is one, becomes available.  -2 on bad arguments, as below.
 int launch_ring_append(const LiveArgs& a, const float* chunk, int n, int flush, hipStream_t st);
 int launch_gather_windows_ring(const LiveArgs& a, bf16_t* out, int64_t* lab_out, int lab_w, hipStream_t st);
-// launch_window_probs' two forms; table [nrows][K], nrows >= Jcap * nf; advances next by the valid rows
+// launch_window_probs' two forms; table [nrows][pitch], nrows >= Jcap * nf.  Without a selection pitch = K and next
+// advances by the valid rows; with one pitch = K + 1 -- columns 0 .. K - 1 the probabilities, column K 1.0,
+// "evaluated" -- and the cursor advances by one
 int launch_live_probs(const LiveArgs& a, const float* src, int softmax, int T, const int* ncls, int K, float* table,
-                      int64_t nrows, int Jcap, hipStream_t st);
+                      int64_t nrows, int pitch, int Jcap, hipStream_t st);
 struct LiveMapArgs {
   const float* table;  // ring table [Jcap * nf][K]
   const int* fs;       // device copy of the fiber start table
@@ -447,14 +453,10 @@ int launch_live_map(const LiveMapArgs& a, int64_t nrows, const int* h_fs, const 
 // (j mod Jcap) * nf + a like the probability table: the windows' powers, their noise floors (the causal running lower
 // median of the last `history` powers of the fiber start, 0 before `warmup` of them exist) and their flags.
 struct LiveGateArgs {
-  LiveArgs live;
+  LiveArgs live;       // live_select writes the selection live.s of the range and resets live.cursor
   float* power;        // [Jcap * nf]
   float* floor;        // [Jcap * nf]
   uint8_t* active;     // [Jcap * nf]
-  int64_t* sel;        // [cap]: the active window numbers of the last selected range, ascending
-  int64_t cap;
-  int64_t* cursor;     // device scalars of the selection: the batch cursor of its replays and its count; they live
-  int64_t* count;      // in a tensor of their own (live_state stays LIVE_NSTATE scalars)
   int Jcap;
   int64_t n0, n1;      // the window numbers of the launch: whole time indices, n0 = j0 * nf, n1 = j1 * nf
 };
@@ -468,12 +470,6 @@ int launch_running_floor(const LiveGateArgs& a, int history, int warmup, hipStre
 // select_blocks(n1 - n0) entries
 int launch_live_select(const LiveGateArgs& a, float ratio, float* table, int64_t nrows, int pitch, int64_t* offs,
                        int64_t noffs, hipStream_t st);
-// gather_windows_ring with batch row r = window sel[cursor * B + r] while that entry is below count (padding beyond)
-int launch_gather_windows_ring_sel(const LiveGateArgs& a, bf16_t* out, int64_t* lab_out, int lab_w, hipStream_t st);
-// live_probs over the selection into a table [nrows >= Jcap * nf][pitch = K + 1]: columns 0 .. K - 1 the
-// probabilities, column K 1.0; then cursor += 1
-int launch_live_probs_sel(const LiveGateArgs& a, const float* src, int softmax, int T, const int* ncls, int K,
-                          float* table, int64_t nrows, int pitch, hipStream_t st);
 // synth.hip: on-device synthetic DAS samples (data/synthetic.py physical model, Philox noise)
 constexpr int SYNTH_NPARAM = 9;  // per sample: distance, event, x0, t0, jitter[4], snr_db
 struct SynthArgs {

@@ -8,6 +8,10 @@
 // live_probs: the probability element of window_batch.h for that numbering, into a ring table [Jcap * nf][K] at row
 //   (j mod Jcap) * nf + a; it then advances next by the number of valid rows, so the replays of one captured graph
 //   need no host copy between them.
+// Both take the batch rows numbered by a live selection (LiveArgs::s and cursor, written by live_gate.hip's
+//   live_select) instead: row r is window sel[cursor * B + r] while that entry is below the count.  The gated table
+//   has K + 1 columns -- the probabilities and 1.0 for an evaluated window, so live_map serves the gated map with
+//   K + 1 classes -- and the store advances the cursor by one.
 // live_map: the gather form of the cell map (window.hip window_map_kernel) for a range of final cell columns, read
 //   from the ring table.
 //
@@ -54,49 +58,62 @@ int launch_ring_append(const LiveArgs& a, const float* chunk, int n, int flush, 
   return (int)hipGetLastError();
 }
 
-// The ring as a gather source is window_batch.h's RingSource: batch row b is window next + b.
+// The window number of batch row r: next + r, or the selection's entry in replay *cursor (-1: padding).
+struct RingNumbering {
+  const LiveArgs& a;
+  const int64_t first, count;  // next, or the selection's batch cursor and count
+  DEV explicit RingNumbering(const LiveArgs& a)
+      : a(a), first(a.s.sel ? *a.cursor : a.state[LIVE_NEXT]), count(a.s.sel ? *a.s.count : 0) {}
+  DEV int64_t operator()(int r) const {
+    return a.s.sel ? selected_number(a.s, first, count, a.g.B, r) : first + r;
+  }
+};
+
+// The ring as a gather source is window_batch.h's RingSource.
 __global__ __launch_bounds__(256) void gather_windows_ring_kernel(LiveArgs a, bf16_t* __restrict__ out,
                                                                   int64_t* __restrict__ lab_out, int lab_w) {
-  const int64_t* s = a.state;
-  gather_windows_body(a.g, RingSource{a, s[LIVE_NEXT], s[LIVE_AVAIL], s[LIVE_JEND], s[LIVE_TEND]}, out, lab_out,
-                      lab_w);
+  gather_windows_body(a.g, RingSource(a), RingNumbering(a), out, lab_out, lab_w);
 }
 
 int launch_gather_windows_ring(const LiveArgs& a, bf16_t* out, int64_t* lab_out, int lab_w, hipStream_t st) {
-  if (!live_args_ok(a) || !gather_geom_ok(a.g, out, lab_out, lab_w)) return -2;
+  if (!live_args_ok(a) || !gather_geom_ok(a.g, out, lab_out, lab_w) || !live_selection_ok(a)) return -2;
   return launch_gather(gather_windows_ring_kernel, a, out, lab_out, lab_w, st);
 }
 
-// One block, as window_probs_kernel.  Row r of the batch is window next + r = (j, a) and goes to table row
-// (j mod Jcap) * nf + a; padding rows are skipped.  next is advanced by thread 0 after every thread has read it (the
-// block barrier).
+// One block, as window_probs_kernel.  Row r of the batch is window (j, a) and goes to table row
+// (j mod Jcap) * nf + a; padding rows are skipped.  Without a selection the table's pitch is K and next advances by
+// the valid rows; with one it is K + 1, column K of an evaluated window is 1, and the cursor advances by one.
+// Thread 0 advances after every thread has read the counter (the block barrier).
 __global__ __launch_bounds__(256) void live_probs_kernel(LiveArgs a, const float* __restrict__ src, int softmax, int T,
-                                                         int4 ncls, int K, float* __restrict__ table, int Jcap) {
-  const int64_t next = a.state[LIVE_NEXT], avail = a.state[LIVE_AVAIL];
+                                                         int4 ncls, int K, float* __restrict__ table, int pitch,
+                                                         int Jcap) {
+  const RingNumbering num(a);
+  const int64_t avail = a.state[LIVE_AVAIL];
   const int nc[4] = {ncls.x, ncls.y, ncls.z, ncls.w};
-  for (int i = threadIdx.x; i < a.g.B * K; i += 256) {
-    const int r = i / K, c = i - r * K;
-    const int64_t n = next + r;
+  for (int i = threadIdx.x; i < a.g.B * pitch; i += 256) {
+    const int r = i / pitch, c = i - r * pitch;
+    const int64_t n = num(r);
     if (n < 0 || n >= avail) continue;
-    const float p = window_prob(src, softmax, T, nc, K, a.g.B, r, c);
-    const int64_t wj = n / a.g.nf;
-    const int64_t row = (wj % Jcap) * a.g.nf + (n - wj * a.g.nf);
-    table[row * K + c] = p;
+    table[ring_row(a.g.nf, Jcap, n) * pitch + c] = c < K ? window_prob(src, softmax, T, nc, K, a.g.B, r, c) : 1.f;
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const int64_t left = avail - next;
-    a.state[LIVE_NEXT] = next + (left < 0 ? 0 : left < a.g.B ? left : a.g.B);
+  if (threadIdx.x != 0) return;
+  if (a.s.sel) {
+    *a.cursor = num.first + 1;
+  } else {
+    const int64_t left = avail - num.first;
+    a.state[LIVE_NEXT] = num.first + (left < 0 ? 0 : left < a.g.B ? left : a.g.B);
   }
 }
 
 int launch_live_probs(const LiveArgs& a, const float* src, int softmax, int T, const int* ncls, int K, float* table,
-                      int64_t nrows, int Jcap, hipStream_t st) {
+                      int64_t nrows, int pitch, int Jcap, hipStream_t st) {
   int4 nc;
-  if (!a.state || !src || !table || K < 1 || a.g.B < 1 || a.g.nf < 1 || Jcap < 1 ||
-      nrows < (int64_t)Jcap * a.g.nf || (int64_t)a.g.B * K >= (1ll << 31) || !pack_ncls(softmax, T, ncls, K, nc))
+  if (!a.state || !live_selection_ok(a) || !src || !table || K < 1 || pitch != K + (a.s.sel ? 1 : 0) || a.g.B < 1 ||
+      a.g.nf < 1 || Jcap < 1 || nrows < (int64_t)Jcap * a.g.nf || (int64_t)a.g.B * pitch >= (1ll << 31) ||
+      !pack_ncls(softmax, T, ncls, K, nc))
     return -2;
-  hipLaunchKernelGGL(live_probs_kernel, dim3(1), dim3(256), 0, st, a, src, softmax, T, nc, K, table, Jcap);
+  hipLaunchKernelGGL(live_probs_kernel, dim3(1), dim3(256), 0, st, a, src, softmax, T, nc, K, table, pitch, Jcap);
   return (int)hipGetLastError();
 }
 

@@ -17,28 +17,23 @@
 //   numbers by the same three launches (block counts, one-block scan, ranked scatter).  The flags launch also zeroes
 //   the table rows of the range: ring-table rows are recycled, and a quiet window must not inherit the probabilities
 //   of the window Jcap indices earlier.  The scatter sets the batch cursor to 0 and LIVE_NEXT to n1.
-// gather_windows_ring_sel / live_probs_sel: the captured step's ends over the selection -- batch row r of replay cur
-//   is window sel[cur * B + r] while that entry is below the count.  The gated table has K + 1 columns: the
-//   probabilities and 1.0 for an evaluated window, so live_map serves the gated map with K + 1 classes.
+// What the selection numbers -- the batch rows of the captured step's gather_windows_ring / live_probs -- is live.hip's,
+// which takes it as LiveArgs::s and cursor.
 #include "window_batch.h"
 
 namespace mda {
 
 namespace {
 
-DEV int64_t ring_row(const LiveGateArgs& a, int64_t n) {
-  const int64_t wj = n / a.live.g.nf;
-  return (wj % a.Jcap) * a.live.g.nf + (n - wj * a.live.g.nf);
-}
+DEV int64_t ring_row(const LiveGateArgs& a, int64_t n) { return mda::ring_row(a.live.g.nf, a.Jcap, n); }
 
 // One block per window, grid-stride over [n0, n1).  A window that cannot be read -- not available yet, outside the
 // fiber, or no longer (not yet) inside the ring's R newest samples -- has no power: NaN, which the selection keeps.
 __global__ __launch_bounds__(256) void ring_window_power_kernel(LiveGateArgs a) {
   __shared__ double s_red[256];
-  const int64_t* s = a.live.state;
-  const int64_t total = s[LIVE_TOTAL];
+  const int64_t total = a.live.state[LIVE_TOTAL];
   const WindowGeom& g = a.live.g;
-  const RingSource src{a.live, 0, s[LIVE_AVAIL], s[LIVE_JEND], s[LIVE_TEND]};
+  const RingSource src(a.live);
   for (int64_t n = a.n0 + blockIdx.x; n < a.n1; n += gridDim.x) {
     int f0;
     int64_t t0;
@@ -99,70 +94,17 @@ __global__ __launch_bounds__(256) void live_flags_kernel(LiveGateArgs a, float r
   }
 }
 
-__global__ __launch_bounds__(256) void live_scan_kernel(int64_t* __restrict__ offs, int64_t nblocks,
-                                                        int64_t* __restrict__ count) {
-  __shared__ int64_t s_sum[256];
-  select_scan_body(offs, nblocks, count, s_sum);
-}
-
 // Block i writes its active windows from sel[offs[i]] on (ranked_place); the step's counters start over.
 __global__ __launch_bounds__(256) void live_scatter_kernel(LiveGateArgs a, const int64_t* __restrict__ offs) {
   __shared__ int s_wave[4];
   const int64_t n = a.n0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
   const bool on = n < a.n1 && a.active[ring_row(a, n)] != 0;
   const int64_t at = ranked_place(on, offs[blockIdx.x], s_wave);
-  if (on && at < a.cap) a.sel[at] = n;  // (at < count <= n1 - n0 <= cap: the launcher checks the capacity)
+  if (on && at < a.live.s.cap) a.live.s.sel[at] = n;  // (at < count <= n1 - n0 <= cap: the launcher's check)
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    *a.cursor = 0;
+    *a.live.cursor = 0;
     a.live.state[LIVE_NEXT] = a.n1;
   }
-}
-
-// The selection over the ring as a gather source: batch row b of replay cur is entry cur * B + b of sel, while that
-// is below the count; the window's start is RingSource's.
-struct SelectedRingSource {
-  using time_type = int64_t;
-  const RingSource ring;
-  const LiveGateArgs& a;
-  const int64_t cur, count;
-  // the window number of batch row r, -1 for padding (an entry past the count or the capacity)
-  DEV int64_t selected(int r) const {
-    const int64_t i = cur * a.live.g.B + r;
-    return (cur < 0 || i >= count || i >= a.cap) ? -1 : a.sel[i];
-  }
-  DEV bool window(int b, int& f0, int64_t& t0) const { return ring.numbered(selected(b), f0, t0); }
-  DEV int64_t column(int64_t t) const { return ring.column(t); }
-  DEV const float* base() const { return ring.base(); }
-  DEV int64_t pitch() const { return ring.pitch(); }
-};
-
-DEV SelectedRingSource selected_source(const LiveGateArgs& a) {
-  const int64_t* s = a.live.state;
-  return SelectedRingSource{RingSource{a.live, 0, s[LIVE_AVAIL], s[LIVE_JEND], s[LIVE_TEND]}, a, *a.cursor,
-                            *a.count};
-}
-
-__global__ __launch_bounds__(256) void gather_windows_ring_sel_kernel(LiveGateArgs a, bf16_t* __restrict__ out,
-                                                                      int64_t* __restrict__ lab_out, int lab_w) {
-  gather_windows_body(a.live.g, selected_source(a), out, lab_out, lab_w);
-}
-
-// One block, as live_probs_kernel, over the selection and a table of pitch K + 1: column K of an evaluated window is
-// 1.  The cursor is advanced by thread 0 after every thread has read it (the block barrier).
-__global__ __launch_bounds__(256) void live_probs_sel_kernel(LiveGateArgs a, const float* __restrict__ src,
-                                                             int softmax, int T, int4 ncls, int K,
-                                                             float* __restrict__ table) {
-  const SelectedRingSource s = selected_source(a);
-  const int nc[4] = {ncls.x, ncls.y, ncls.z, ncls.w};
-  const int pitch = K + 1;
-  for (int i = threadIdx.x; i < a.live.g.B * pitch; i += 256) {
-    const int r = i / pitch, c = i - r * pitch;
-    const int64_t n = s.selected(r);
-    if (n < 0 || n >= s.ring.avail) continue;
-    table[ring_row(a, n) * pitch + c] = c < K ? window_prob(src, softmax, T, nc, K, a.live.g.B, r, c) : 1.f;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) *a.cursor = s.cur + 1;
 }
 
 // [n0, n1) is a range of whole time indices that fits the rings
@@ -173,8 +115,6 @@ bool range_ok(const LiveGateArgs& a) {
 }
 
 unsigned window_blocks(const LiveGateArgs& a) { return (unsigned)std::min<int64_t>(a.n1 - a.n0, 65535); }
-
-bool selection_ok(const LiveGateArgs& a) { return a.live.state && a.sel && a.cursor && a.count && a.cap >= 0 && a.Jcap >= 1; }
 
 }  // namespace
 
@@ -200,34 +140,17 @@ int launch_running_floor(const LiveGateArgs& a, int history, int warmup, hipStre
 
 int launch_live_select(const LiveGateArgs& a, float ratio, float* table, int64_t nrows, int pitch, int64_t* offs,
                        int64_t noffs, hipStream_t st) {
-  if (!selection_ok(a) || !a.power || !a.floor || !a.active || !table || !offs || !range_ok(a) ||
-      a.cap < a.n1 - a.n0 || pitch < 1 || pitch > (1 << 16) || nrows < (int64_t)a.Jcap * a.live.g.nf ||
-      noffs < select_blocks(a.n1 - a.n0) || select_blocks(a.n1 - a.n0) >= (1ll << 31))
+  // the selection is written here: it has to be there, whole
+  if (!a.live.state || !a.live.s.sel || !live_selection_ok(a.live) || !a.power || !a.floor || !a.active || !table ||
+      !offs || !range_ok(a) || a.live.s.cap < a.n1 - a.n0 || pitch < 1 || pitch > (1 << 16) ||
+      nrows < (int64_t)a.Jcap * a.live.g.nf || noffs < select_blocks(a.n1 - a.n0) ||
+      select_blocks(a.n1 - a.n0) >= (1ll << 31))
     return -2;
   if (a.n1 == a.n0) return 0;
   const unsigned blocks = (unsigned)select_blocks(a.n1 - a.n0);
   hipLaunchKernelGGL(live_flags_kernel, dim3(blocks), dim3(256), 0, st, a, ratio, table, pitch, offs);
-  hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(256), 0, st, offs, (int64_t)blocks, a.count);
+  launch_select_scan(offs, (int64_t)blocks, a.live.s.count, st);
   hipLaunchKernelGGL(live_scatter_kernel, dim3(blocks), dim3(256), 0, st, a, (const int64_t*)offs);
-  return (int)hipGetLastError();
-}
-
-int launch_gather_windows_ring_sel(const LiveGateArgs& a, bf16_t* out, int64_t* lab_out, int lab_w, hipStream_t st) {
-  if (!live_args_ok(a.live) || !gather_geom_ok(a.live.g, out, lab_out, lab_w) || !selection_ok(a)) return -2;
-  const int64_t M = (int64_t)a.live.g.B * a.live.g.Wf * a.live.g.Wt;
-  const int blocks = (int)std::min<int64_t>((M + 255) / 256, 65535);
-  hipLaunchKernelGGL(gather_windows_ring_sel_kernel, dim3(blocks), dim3(256), 0, st, a, out, lab_out, lab_w);
-  return (int)hipGetLastError();
-}
-
-int launch_live_probs_sel(const LiveGateArgs& a, const float* src, int softmax, int T, const int* ncls, int K,
-                          float* table, int64_t nrows, int pitch, hipStream_t st) {
-  int4 nc;
-  if (!selection_ok(a) || !src || !table || K < 1 || pitch != K + 1 || a.live.g.B < 1 || a.live.g.nf < 1 ||
-      nrows < (int64_t)a.Jcap * a.live.g.nf || (int64_t)a.live.g.B * pitch >= (1ll << 31) ||
-      !pack_ncls(softmax, T, ncls, K, nc))
-    return -2;
-  hipLaunchKernelGGL(live_probs_sel_kernel, dim3(1), dim3(256), 0, st, a, src, softmax, T, nc, K, table);
   return (int)hipGetLastError();
 }
 

@@ -9,25 +9,35 @@
 // window_map: a sample's value is the mean of the windows covering it, a cell's the mean of its samples; computed
 //   in gather form (one thread per output, fixed summation order): deterministic, no atomics.
 //
-// The gather body, the probability element, the covering windows and weight bands of a cell, and the launchers'
-// common checks are window_batch.h's, shared with live.hip.
+// Both launches take the batch rows numbered by an on-device selection (WindowArgs::s, written by gate.hip's
+// select_windows) in place of idx or the consecutive cursor form: the launcher sees it from the pointers, the kernel
+// branches on them.  The count is read on the device, so one captured graph serves any selection.
+//
+// The gather body, the selected numbering, the probability element, the covering windows and weight bands of a cell,
+// and the launchers' common checks are window_batch.h's, shared with live.hip.
 #include "window_batch.h"
 
 namespace mda {
 
-// The window number of batch row r: idx[r], or lo + cursor * B + r.  Rows outside [lo, hi) are padding.
-DEV int64_t window_number(const WindowArgs& a, int64_t cur, int r) {
-  return a.idx ? a.idx[r] : a.lo + cur * a.g.B + r;
-}
+// The window number of batch row r: the selection's entry, idx[r], or lo + cursor * B + r.  Numbers outside
+// [lo, hi) are padding.
+struct WindowNumbering {
+  const WindowArgs& a;
+  const int64_t cur, count;
+  DEV explicit WindowNumbering(const WindowArgs& a)
+      : a(a), cur(a.cursor ? *a.cursor : 0), count(a.s.sel ? *a.s.count : 0) {}
+  DEV int64_t operator()(int r) const {
+    if (a.s.sel) return selected_number(a.s, cur, count, a.g.B, r);
+    return a.idx ? a.idx[r] : a.lo + cur * a.g.B + r;
+  }
+};
 
-// The recording as a gather source: window n = a * nt + b starts at (fs[a], ts[b]) and has to end inside the
-// recording; time t is column t.
+// The recording as a gather source: window n = a * nt + b of [lo, hi) starts at (fs[a], ts[b]) and has to end inside
+// the recording; time t is column t.
 struct RecordingSource {
   using time_type = int;
   const WindowArgs& a;
-  const int64_t cur;
-  DEV bool window(int b, int& f0, int& t0) const {
-    const int64_t n = window_number(a, cur, b);
+  DEV bool numbered(int64_t n, int& f0, int& t0) const {
     if (n < a.lo || n >= a.hi) return false;
     const int wa = (int)(n / a.nt), wb = (int)(n - (int64_t)wa * a.nt);
     f0 = a.g.fs[wa];
@@ -41,12 +51,14 @@ struct RecordingSource {
 
 __global__ __launch_bounds__(256) void gather_windows_kernel(WindowArgs a, bf16_t* __restrict__ out,
                                                              int64_t* __restrict__ lab_out, int lab_w) {
-  gather_windows_body(a.g, RecordingSource{a, a.cursor ? *a.cursor : 0}, out, lab_out, lab_w);
+  gather_windows_body(a.g, RecordingSource{a}, WindowNumbering(a), out, lab_out, lab_w);
 }
 
-// what gather_windows and window_probs both need of the numbering
+// what gather_windows and window_probs both need of the numbering: exactly one of idx / cursor, and a selection
+// only whole and with the cursor (so without idx)
 static bool numbering_ok(const WindowArgs& a) {
-  return a.g.B >= 1 && a.lo >= 0 && a.lo <= a.hi && (a.idx == nullptr) != (a.cursor == nullptr);
+  return a.g.B >= 1 && a.lo >= 0 && a.lo <= a.hi && (a.idx == nullptr) != (a.cursor == nullptr) &&
+         selection_ok(a.s) && !(a.s.sel && !a.cursor);
 }
 
 int launch_gather_windows(const WindowArgs& a, bf16_t* out, int64_t* lab_out, int lab_w, hipStream_t st) {
@@ -60,17 +72,17 @@ int launch_gather_windows(const WindowArgs& a, bf16_t* out, int64_t* lab_out, in
 // advanced by thread 0 after every thread has read it (the block barrier).
 __global__ __launch_bounds__(256) void window_probs_kernel(WindowArgs a, const float* __restrict__ src, int softmax,
                                                            int T, int4 ncls, int K, float* __restrict__ probs) {
-  const int64_t cur = a.cursor ? *a.cursor : 0;
+  const WindowNumbering num(a);
   const int nc[4] = {ncls.x, ncls.y, ncls.z, ncls.w};
   for (int i = threadIdx.x; i < a.g.B * K; i += 256) {
     const int r = i / K, c = i - r * K;
-    const int64_t n = window_number(a, cur, r);
+    const int64_t n = num(r);
     if (n < a.lo || n >= a.hi) continue;
     probs[n * K + c] = window_prob(src, softmax, T, nc, K, a.g.B, r, c);
   }
   if (a.cursor) {
     __syncthreads();
-    if (threadIdx.x == 0) *a.cursor = cur + 1;
+    if (threadIdx.x == 0) *a.cursor = num.cur + 1;
   }
 }
 

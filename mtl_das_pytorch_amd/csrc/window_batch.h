@@ -2,31 +2,46 @@
 // recording whose time axis is a ring (live.hip).  One copy of
 //
 //   * the gather body: the NHWC-8 pixel loop with the stem's tap packing and the window-edge padding, a template
-//     over the source (where batch row b's window starts, which column holds time t, base pointer and row pitch);
-//   * the ring as a source (RingSource), the window power body (a template over the source, so the ring's powers
-//     have the bits of the linear recording's) and the ordered selection's count / scan / rank pieces, shared by
-//     the two activity gates (gate.hip, live_gate.hip);
+//     over two separate things: the numbering (which window number batch row b holds, or that it is padding) and
+//     the source (where window n starts, which column holds time t, base pointer and row pitch);
+//   * the selected numbering, the one both sources and both probability kernels use when the launch carries a
+//     Selection: entry cur * B + r of sel while below the count and the capacity;
+//   * the ring as a source (RingSource) and its table row, the window power body (a template over the source, so
+//     the ring's powers have the bits of the linear recording's) and the ordered selection's count / scan / rank
+//     pieces, shared by the two activity gates (gate.hip, live_gate.hip);
 //   * the probability element: softmax of a logits row, or exp of the owning task's log-probability;
 //   * the fiber side of the maps: the windows covering a cell (bisection) and the weight-band lookup;
-//   * the launchers' common checks: the batch geometry, the ncls packing, "the starts cover the axis".
+//   * the launchers' common checks: the batch geometry, the selection, the ncls packing, "the starts cover the axis".
 //
-// What differs stays in the kernels: how a batch row is numbered and where its probabilities go, the counter
-// advance, and the maps' time loops (bands over ts in window.hip, per-column weight vectors over the ring table in
-// live.hip).  The maps' sums `acc += (wf * wt) * p` are written out in each kernel: their rounding is the kernel's.
+// What differs stays in the kernels: the unselected numberings (idx / cursor in window.hip, next in live.hip), where
+// a row's probabilities go, the counter advance, and the maps' time loops (bands over ts in window.hip, per-column
+// weight vectors over the ring table in live.hip).  The maps' sums `acc += (wf * wt) * p` are written out in each
+// kernel: their rounding is the kernel's.
 #pragma once
 #include "kernels.h"
 
 namespace mda {
 
+// The selected numbering: the window number of batch row r in replay cur, -1 for padding (an entry past the count
+// or the capacity).  count is *s.count, read once by the kernel.
+DEV int64_t selected_number(const Selection& s, int64_t cur, int64_t count, int B, int r) {
+  const int64_t i = cur * B + r;
+  return (cur < 0 || i >= count || i >= s.cap) ? -1 : s.sel[i];
+}
+
+// sel and count come together (the launcher adds what it requires of the cursor)
+inline bool selection_ok(const Selection& s) { return (s.sel == nullptr) == (s.count == nullptr) && s.cap >= 0; }
+
 // One thread per output pixel, threads along t (the source's contiguous axis).  The padding of the tap packing is
 // the window's: channel j of pixel (h, w) is x[h - off + j][w] inside the window, zero outside it even where the
-// source has rows there.  A batch row that is no window (src.window false: padding, or a start outside the source)
-// is written as zeros and reads nothing.  Source:
-//   bool window(int b, int& f0, T& t0)   batch row b is a window, starting at fiber row f0 and time t0
-//   int64_t column(t)                    the column of the source that holds time t
-//   const float* base(); int64_t pitch() the source is [C][F][pitch] fp32
-template <class Source>
-DEV void gather_windows_body(const WindowGeom& g, const Source& src, bf16_t* __restrict__ out,
+// source has rows there.  A batch row that is no window (padding, a number the source does not have, or a start
+// outside the source) is written as zeros and reads nothing.
+//   int64_t num(int b)                           the window number of batch row b; padding is a number no source has
+//   bool src.numbered(int64_t n, int& f0, T& t0) window n exists, starting at fiber row f0 and time t0
+//   int64_t src.column(t)                        the column of the source that holds time t
+//   const float* src.base(); int64_t src.pitch() the source is [C][F][pitch] fp32
+template <class Source, class Numbering>
+DEV void gather_windows_body(const WindowGeom& g, const Source& src, const Numbering& num, bf16_t* __restrict__ out,
                              int64_t* __restrict__ lab_out, int lab_w) {
   const int HW = g.Wf * g.Wt;
   const int64_t M = (int64_t)g.B * HW;
@@ -41,7 +56,7 @@ DEV void gather_windows_body(const WindowGeom& g, const Source& src, bf16_t* __r
     for (int j = 0; j < 8; ++j) v[j] = 0.f;
     int f0;
     typename Source::time_type t0;
-    if (src.window(b, f0, t0) && f0 >= 0 && f0 + g.Wf <= g.F) {
+    if (src.numbered(num(b), f0, t0) && f0 >= 0 && f0 + g.Wf <= g.F) {
       const int64_t col = src.column(t0 + w);
       if (g.taps > 0) {
 #pragma unroll
@@ -78,13 +93,14 @@ int launch_gather(Kernel kernel, const Args& a, bf16_t* out, int64_t* lab_out, i
   return (int)hipGetLastError();
 }
 
-// The ring as a gather source (live.hip, live_gate.hip): window n = (j, a) exists while n is below avail; it starts at
-// fiber row fs[a] and time j * st (tend for the end-aligned index jend); time t is column t mod R.  Batch row b is
-// window next + b.
+// The ring as a source (live.hip, live_gate.hip): window n = (j, a) exists while n is in [0, avail); it starts at
+// fiber row fs[a] and time j * st (tend for the end-aligned index jend); time t is column t mod R.
 struct RingSource {
   using time_type = int64_t;
   const LiveArgs& a;
-  const int64_t next, avail, jend, tend;
+  const int64_t avail, jend, tend;
+  DEV explicit RingSource(const LiveArgs& a)
+      : a(a), avail(a.state[LIVE_AVAIL]), jend(a.state[LIVE_JEND]), tend(a.state[LIVE_TEND]) {}
   DEV bool numbered(int64_t n, int& f0, int64_t& t0) const {
     if (n < 0 || n >= avail) return false;
     const int64_t wj = n / a.g.nf;
@@ -92,16 +108,26 @@ struct RingSource {
     t0 = wj == jend ? tend : wj * a.st;
     return t0 >= 0;
   }
-  DEV bool window(int b, int& f0, int64_t& t0) const { return numbered(next + b, f0, t0); }
   DEV int64_t column(int64_t t) const { return t % a.R; }
   DEV const float* base() const { return a.ring; }
   DEV int64_t pitch() const { return a.R; }
 };
 
+// the row of window n = (j, a) in a ring of Jcap time indices (the probability table, the gate's rings)
+DEV int64_t ring_row(int nf, int Jcap, int64_t n) {
+  const int64_t wj = n / nf;
+  return (wj % Jcap) * nf + (n - wj * nf);
+}
+
 // what every launch over the ring requires of it
 inline bool live_args_ok(const LiveArgs& a) {
   return a.state && a.ring && a.g.C >= 1 && a.g.F >= 1 && a.g.nf >= 1 && a.st >= 1 && a.g.Wt >= 1 &&
          a.R >= (int64_t)a.g.Wt + 1;
+}
+
+// the ring's selection brings its own batch cursor: all of sel, count and cursor, or none
+inline bool live_selection_ok(const LiveArgs& a) {
+  return selection_ok(a.s) && (a.s.sel == nullptr) == (a.cursor == nullptr);
 }
 
 // the 256 partial sums in a fixed tree order; every thread returns the total
@@ -163,27 +189,9 @@ DEV int block_flag_count(bool on, int* s_wave) {
   return s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
 }
 
-// One block: the block counts become their exclusive prefix sums (in place, 256 at a time with a carry), the total
-// becomes the count.
-DEV void select_scan_body(int64_t* __restrict__ offs, int64_t nblocks, int64_t* __restrict__ count, int64_t* s_sum) {
-  int64_t carry = 0;
-  for (int64_t base = 0; base < nblocks; base += 256) {
-    const int64_t i = base + threadIdx.x;
-    const int64_t own = i < nblocks ? offs[i] : 0;
-    s_sum[threadIdx.x] = own;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {  // inclusive scan
-      const int64_t v = threadIdx.x >= o ? s_sum[threadIdx.x - o] : 0;
-      __syncthreads();
-      s_sum[threadIdx.x] += v;
-      __syncthreads();
-    }
-    if (i < nblocks) offs[i] = carry + s_sum[threadIdx.x] - own;
-    carry += s_sum[255];
-    __syncthreads();  // (s_sum[255] is read before the next round overwrites it)
-  }
-  if (threadIdx.x == 0) *count = carry;
-}
+// The second of the three launches, one block (select_scan_kernel, gate.hip): the block counts become their exclusive
+// prefix sums, the total becomes the count.
+void launch_select_scan(int64_t* offs, int64_t nblocks, int64_t* count, hipStream_t st);
 
 // The place of this thread's candidate among the set flags: those of the blocks before (block_off), of the block's
 // waves before (the ballots' counts), of the wave's lanes below (mbcnt).  Every thread of the 256 calls it; the

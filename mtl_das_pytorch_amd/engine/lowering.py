@@ -17,8 +17,6 @@ from .program import (COMM_STREAM, SPILL_STREAM, Launch, Phase, k_adam, k_step_i
                       k_wgrad_batched, k_window_probs)
 from .program import NoiseSpec, k_gather_noise, k_noise_advance
 from .program import k_gather_windows_ring, k_live_probs
-from .program import k_gather_windows_sel, k_window_probs_sel
-from .program import k_gather_windows_ring_sel, k_live_probs_sel
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID, SIGMUL, ADD_RELU, POOL_RELU = range(6)
 
@@ -479,13 +477,9 @@ class LoweredProgram:
         d = self._window_args(idx, cursor, lo, fs.numel() * ts.numel() if hi is None else hi)
         d.update(self._stem_fields(rec, fs))
         d.update({"rec": P(rec), "ts": P(ts), "T": rec.shape[2], "nt": ts.numel()})
-        s = selection_args(sel, count, idx, cursor)
-        d.update(s)
+        d.update(selection_args(sel, count, idx, cursor))
         ph = Phase("window_gather")
-        if s:
-            ph.add("gather_windows_sel", k_gather_windows_sel, d)
-        else:
-            ph.add("gather_windows", k_gather_windows, d)
+        ph.add("gather_windows", k_gather_windows, d)
         ph.keep = (rec, fs, ts, idx, cursor, sel, count)  # the launch holds their device pointers
         return ph
 
@@ -520,27 +514,11 @@ class LoweredProgram:
         d = self._prob_fields(probs)
         d.update(self._window_args(idx, cursor, lo, probs.shape[0] if hi is None else hi))
         d.update({"probs": P(probs), "nprobs": probs.shape[0]})
-        s = selection_args(sel, count, idx, cursor)
-        d.update(s)
+        d.update(selection_args(sel, count, idx, cursor))
         ph = Phase("window_probs")
-        if s:
-            ph.add("window_probs_sel", k_window_probs_sel, d)
-        else:
-            ph.add("window_probs", k_window_probs, d)
+        ph.add("window_probs", k_window_probs, d)
         ph.keep = (probs, idx, cursor, sel, count)
         return ph
-
-    def _live_selection(self, sel, count, cursor) -> dict:
-        """The launch fields of a gated live step, empty without a selection: ``sel`` (device int64 window numbers),
-        ``count`` and ``cursor`` (device int64 scalars; ops.functional.live_gate_state) come together."""
-        if sel is None and count is None and cursor is None:
-            return {}
-        if sel is None or count is None or cursor is None:
-            raise ValueError("a live selection is sel, count and cursor together")
-        self._device_vector(sel, torch.int64, "the selection")
-        self._device_vector(count, torch.int64, "the selection's count", 1)
-        self._device_vector(cursor, torch.int64, "the selection's cursor", 1)
-        return {"sel": P(sel), "cap": sel.numel(), "count": P(count), "cursor": P(cursor), "Jcap": 1}
 
     def live_gather_phase(self, ring, fs, state, st: int, sel=None, count=None, cursor=None) -> Phase:
         """The batch gather of live inference: the batch's (H0, W0) windows are cut from the time ring ``ring``
@@ -557,13 +535,9 @@ class LoweredProgram:
         self._device_vector(state, torch.int64, "the live scalars (live_state)", LIVE_NSTATE)
         d = self._stem_fields(ring, fs)
         d.update({"ring": P(ring), "state": P(state), "R": ring.shape[2], "st": int(st)})
-        s = self._live_selection(sel, count, cursor)
-        d.update(s)
+        d.update(selection_args(sel, count, None, cursor, live=True))
         ph = Phase("live_gather")
-        if s:
-            ph.add("gather_windows_ring_sel", k_gather_windows_ring_sel, d)
-        else:
-            ph.add("gather_windows_ring", k_gather_windows_ring, d)
+        ph.add("gather_windows_ring", k_gather_windows_ring, d)
         ph.keep = (ring, fs, state, sel, count, cursor)  # the launch holds their device pointers
         return ph
 
@@ -573,19 +547,16 @@ class LoweredProgram:
         ``count`` / ``cursor``: the rows are numbered by the selection, as in :meth:`live_gather_phase`; the table
         is the gated one, [>= jcap * nf, K + 1] with the "evaluated" column last, and the launch advances the
         cursor by one."""
-        s = self._live_selection(sel, count, cursor)
+        s = selection_args(sel, count, None, cursor, live=True)
         d = self._prob_fields(table, flag_column=bool(s))
         if jcap < 1 or nf < 1 or table.shape[0] < jcap * nf:
             raise ValueError(f"a table of {table.shape[0]} rows is below jcap * nf = {jcap * nf}")
         self._device_vector(state, torch.int64, "the live scalars (live_state)", LIVE_NSTATE)
-        d.update({"state": P(state), "nf": int(nf), "table": P(table), "nrows": table.shape[0], "Jcap": int(jcap)})
+        d.update(s)
+        d.update({"state": P(state), "nf": int(nf), "table": P(table), "nrows": table.shape[0],
+                  "pitch": table.shape[1], "Jcap": int(jcap)})
         ph = Phase("live_probs")
-        if s:
-            d.update(s)
-            d.update({"Jcap": int(jcap), "pitch": table.shape[1]})
-            ph.add("live_probs_sel", k_live_probs_sel, d)
-        else:
-            ph.add("live_probs", k_live_probs, d)
+        ph.add("live_probs", k_live_probs, d)
         ph.keep = (table, state, sel, count, cursor)
         return ph
 

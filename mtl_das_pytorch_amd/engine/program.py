@@ -418,7 +418,8 @@ def k_noise_advance(draw, st):
 
 
 def k_gather_windows(d, st):
-    """The batch's windows cut from a resident recording (csrc/window.hip; ``d``: the launch's argument dict)."""
+    """The batch's windows cut from a resident recording (csrc/window.hip; ``d``: the launch's argument dict, with
+    the selection's fields when the rows are numbered by one)."""
     lib().gather_windows(st, d)
 
 
@@ -427,32 +428,12 @@ def k_window_probs(d, st):
     lib().window_probs(st, d)
 
 
-def k_gather_windows_sel(d, st):
-    """The batch's windows by an on-device selection (csrc/gate.hip): row r is window sel[cursor * B + r]."""
-    lib().gather_windows_sel(st, d)
-
-
-def k_window_probs_sel(d, st):
-    """The selected batch rows' probabilities into the resident table; advances the batch cursor."""
-    lib().window_probs_sel(st, d)
-
-
 def k_gather_windows_ring(d, st):
     """The batch's windows cut from the time ring of a live recording (csrc/live.hip)."""
     lib().gather_windows_ring(st, d)
 
 
 def k_live_probs(d, st):
-    """The batch's probabilities into the live ring table; advances the window counter by the valid rows."""
+    """The batch's probabilities into the live ring table; advances the window counter by the valid rows, or the
+    cursor of the selection the rows are numbered by."""
     lib().live_probs(st, d)
-
-
-def k_gather_windows_ring_sel(d, st):
-    """The batch's windows cut from the time ring by a live selection (csrc/live_gate.hip)."""
-    lib().gather_windows_ring_sel(st, d)
-
-
-def k_live_probs_sel(d, st):
-    """The selected batch rows' probabilities and their "evaluated" column into the gated ring table; advances the
-    batch cursor."""
-    lib().live_probs_sel(st, d)

@@ -70,6 +70,16 @@ def _shard(n: int, ctx: Optional[DistContext]) -> Tuple[int, int]:
     return min(n, ctx.rank * per), min(n, (ctx.rank + 1) * per)
 
 
+def _recording_windows(rec: torch.Tensor, stride, ctx: Optional[DistContext]):
+    """What every form of :func:`predict_recording` starts from: the recording as fp32 [C, F, T], its window starts
+    ``fs`` / ``ts``, the positions [N, 2] of its N windows (window ``n = a * len(ts) + b`` at ``(fs[a], ts[b])``, the
+    order of :func:`sliding_windows`), N and this rank's shard ``(lo, hi)`` of them."""
+    rec3 = rec.float().unsqueeze(0) if rec.dim() == 2 else rec.float()
+    fs, ts = window_starts(rec3.shape[1], WINDOW[0], stride[0]), window_starts(rec3.shape[2], WINDOW[1], stride[1])
+    pos = np.stack(np.meshgrid(fs, ts, indexing="ij"), -1).reshape(-1, 2)
+    return rec3, fs, ts, pos, len(pos), _shard(len(pos), ctx)
+
+
 def _torch_probs(model: nn.Module, model_type: str, x: torch.Tensor) -> Sequence[torch.Tensor]:
     out = model(x)
     if model_type == "multi_classifier":
@@ -95,14 +105,19 @@ def window_power_reference(rec, fs, ts, window: Tuple[int, int] = WINDOW) -> np.
     return out.reshape(-1)
 
 
+def _auto_floor(noise_floor) -> bool:
+    """``noise_floor`` of :func:`predict_recording`: True for ``"auto"``, False for a power; no other string."""
+    if isinstance(noise_floor, str) and noise_floor != "auto":
+        raise ValueError(f"noise_floor must be 'auto' or a power, got {noise_floor!r}")
+    return isinstance(noise_floor, str)
+
+
 def noise_floor_reference(power: np.ndarray, nt: int, noise_floor="auto") -> np.ndarray:
     """The noise floor of every fiber start, fp64 [nf]: a number is one floor for all of them; ``"auto"`` is the lower
     median over time of the start's window powers, ``sorted(power[a, :])[(nt - 1) // 2]`` (noise varies along a
     fiber, and an event is short against a recording)."""
     p = np.asarray(power, dtype=np.float64).reshape(-1, nt)
-    if isinstance(noise_floor, str):
-        if noise_floor != "auto":
-            raise ValueError(f"noise_floor must be 'auto' or a power, got {noise_floor!r}")
+    if _auto_floor(noise_floor):
         return np.sort(p, 1)[:, (nt - 1) // 2]
     return np.full(len(p), float(noise_floor))
 
@@ -185,12 +200,8 @@ def predict_recording(model: nn.Module, model_type: str, rec: torch.Tensor, stri
     if runner is not None and windows != "resident":
         raise ValueError("a window runner serves windows='resident' only")
     names, ncls = _task_names(model, model_type)
+    rec3, fs, ts, pos, n, (lo, hi) = _recording_windows(rec, stride, ctx)
     if windows == "resident":
-        rec3 = rec.float().unsqueeze(0) if rec.dim() == 2 else rec.float()
-        fs, ts = window_starts(rec3.shape[1], WINDOW[0], stride[0]), window_starts(rec3.shape[2], WINDOW[1], stride[1])
-        pos = np.stack(np.meshgrid(fs, ts, indexing="ij"), -1).reshape(-1, 2)
-        n = len(pos)
-        lo, hi = _shard(n, ctx)
         gate = None if gate_db is None else (float(gate_db), noise_floor)
         if runner is not None:
             table = resident_probs(runner, rec3, fs, ts, lo, hi, gate=gate)
@@ -205,11 +216,6 @@ def predict_recording(model: nn.Module, model_type: str, rec: torch.Tensor, stri
     flags = None
     if gate_db is not None:
         # the same gate by the fp64 reference; only the active windows of this rank's shard are stacked
-        rec3 = rec.float().unsqueeze(0) if rec.dim() == 2 else rec.float()
-        fs, ts = window_starts(rec3.shape[1], WINDOW[0], stride[0]), window_starts(rec3.shape[2], WINDOW[1], stride[1])
-        pos = np.stack(np.meshgrid(fs, ts, indexing="ij"), -1).reshape(-1, 2)
-        n = len(pos)
-        lo, hi = _shard(n, ctx)
         power = window_power_reference(rec3, fs, ts)
         flags = (active_reference(power, len(ts), gate_db, noise_floor), power)
         keep = lo + np.flatnonzero(flags[0][lo:hi])
@@ -218,11 +224,8 @@ def predict_recording(model: nn.Module, model_type: str, rec: torch.Tensor, stri
         if len(keep):
             mine = torch.stack([rec3[:, f0:f0 + WINDOW[0], t0:t0 + WINDOW[1]] for f0, t0 in pos[keep]]).to(device)
     else:
-        tiles, pos = sliding_windows(rec.float(), stride=stride)
-        n = len(tiles)
-        lo, hi = _shard(n, ctx)
         rows = slice(lo, hi)
-        mine = tiles[lo:hi].to(device)
+        mine = sliding_windows(rec3, stride=stride)[0][lo:hi].to(device)
     probs = [torch.zeros(n, k, device=device) for k in ncls]
     if len(mine):
         if use_engine:
@@ -347,9 +350,7 @@ def resident_probs(runner, rec: torch.Tensor, fs: np.ndarray, ts: np.ndarray, lo
     gate_db, noise_floor = gate
     nf, nt = len(fs), len(ts)
     power = HF.window_power(rec_d, fs_d, ts_d, WINDOW)
-    if isinstance(noise_floor, str):
-        if noise_floor != "auto":
-            raise ValueError(f"noise_floor must be 'auto' or a power, got {noise_floor!r}")
+    if _auto_floor(noise_floor):
         floor = torch.sort(power.view(nf, nt), 1).values[:, (nt - 1) // 2].contiguous()
     else:
         floor = torch.full((nf,), float(noise_floor), dtype=torch.float32, device=dev)

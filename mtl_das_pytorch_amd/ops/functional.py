@@ -734,20 +734,22 @@ def _prob_source(src: torch.Tensor, K: int, ncls: Optional[Sequence[int]]):
     return B, d
 
 
-def selection_args(sel: Optional[torch.Tensor], count: Optional[torch.Tensor], idx, cursor) -> dict:
-    """The launch fields of a selected window launch (csrc/gate.hip), empty without a selection: ``sel`` (device
+def selection_args(sel: Optional[torch.Tensor], count: Optional[torch.Tensor], idx, cursor,
+                   live: bool = False) -> dict:
+    """The launch fields of a gather / probability launch numbered by a selection, empty without one: ``sel`` (device
     int64 window numbers) and ``count`` (device int64 scalar, how many of them are valid) come together, with a
-    ``cursor`` and without ``idx``."""
-    if sel is None and count is None:
+    ``cursor`` (device int64 scalar) and without ``idx``.  ``live``: the selection of a growing recording
+    (:func:`live_select`), whose cursor is its own (:func:`live_gate_state`) and comes only with it."""
+    if sel is None and count is None and not (live and cursor is not None):
         return {}
     if sel is None or count is None or idx is not None or cursor is None:
         raise ValueError("a selection is sel and count together, with a cursor and without idx")
-    for t in (sel, count):
+    for t in (sel, count, cursor):
         if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
-            raise ValueError("sel / count must be contiguous int64 tensors on the device")
-    if sel.dim() != 1 or count.numel() != 1:
-        raise ValueError("sel must be a vector and count one number")
-    return {"sel": ptr(sel), "count": ptr(count), "cap": sel.numel()}
+            raise ValueError("sel / count / cursor must be contiguous int64 tensors on the device")
+    if sel.dim() != 1 or count.numel() != 1 or cursor.numel() != 1:
+        raise ValueError("sel must be a vector, count and cursor one number each")
+    return {"sel": ptr(sel), "count": ptr(count), "cap": sel.numel(), "cursor": ptr(cursor)}
 
 
 def gather_windows(rec: torch.Tensor, fs, ts, window: Tuple[int, int], B: int, idx: Optional[torch.Tensor] = None,
@@ -778,12 +780,8 @@ def gather_windows(rec: torch.Tensor, fs, ts, window: Tuple[int, int], B: int, i
     d, out, lab = _gather_out(rec.device, fs, window, B, taps, off, lab_w)
     d.update({"rec": ptr(rec), "ts": ptr(ts), "C": C, "F": Fn, "T": Tn, "nt": ts.numel(), "idx": ptr(idx),
               "cursor": ptr(cursor), "lo": lo, "hi": hi})
-    s = selection_args(sel, count, idx, cursor)
-    if s:
-        d.update(s)
-        lib().gather_windows_sel(stream(), d)
-    else:
-        lib().gather_windows(stream(), d)
+    d.update(selection_args(sel, count, idx, cursor))
+    lib().gather_windows(stream(), d)
     return out, lab
 
 
@@ -811,12 +809,8 @@ def window_probs(src: torch.Tensor, probs: torch.Tensor, idx: Optional[torch.Ten
         raise ValueError("idx must hold B window numbers")
     d.update({"idx": ptr(idx), "cursor": ptr(cursor), "lo": lo, "hi": N if hi is None else hi, "probs": ptr(probs),
               "nprobs": N})
-    s = selection_args(sel, count, idx, cursor)
-    if s:
-        d.update(s)
-        lib().window_probs_sel(stream(), d)
-    else:
-        lib().window_probs(stream(), d)
+    d.update(selection_args(sel, count, idx, cursor))
+    lib().window_probs(stream(), d)
     return probs
 
 
@@ -952,19 +946,23 @@ def live_state(device) -> torch.Tensor:
     return s.to(device)
 
 
-def _live_args(ring: torch.Tensor, state: torch.Tensor, nf: int, st: int, Wt: int) -> dict:
-    _check(ring, torch.float32)
+def _live_scalars(state: torch.Tensor) -> int:
     _check(state, torch.int64)
-    if ring.dim() != 3:
-        raise ValueError("ring must be [C, F, R]")
     if state.numel() != LIVE_NSTATE:
         raise ValueError(f"state must hold {LIVE_NSTATE} int64 scalars (live_state)")
+    return ptr(state)
+
+
+def _live_args(ring: torch.Tensor, state: torch.Tensor, nf: int, st: int, Wt: int) -> dict:
+    _check(ring, torch.float32)
+    if ring.dim() != 3:
+        raise ValueError("ring must be [C, F, R]")
     C, Fn, R = ring.shape
     if R < Wt + 1:
         raise ValueError(f"a ring of {R} time columns is below the window's {Wt} + 1")
     if st < 1 or nf < 1:
         raise ValueError("time stride and fiber window count must be positive")
-    return {"ring": ptr(ring), "state": ptr(state), "C": C, "F": Fn, "R": R, "nf": int(nf), "st": int(st),
+    return {"ring": ptr(ring), "state": _live_scalars(state), "C": C, "F": Fn, "R": R, "nf": int(nf), "st": int(st),
             "Wt": int(Wt)}
 
 
@@ -991,40 +989,51 @@ def ring_append(ring: torch.Tensor, state: torch.Tensor, chunk: Optional[torch.T
 
 
 def gather_windows_ring(ring: torch.Tensor, state: torch.Tensor, fs, st: int, window: Tuple[int, int], B: int,
-                        taps: int = 0, off: int = 0, lab_w: int = 2):
+                        taps: int = 0, off: int = 0, lab_w: int = 2, sel: Optional[torch.Tensor] = None,
+                        count: Optional[torch.Tensor] = None, cursor: Optional[torch.Tensor] = None):
     """:func:`gather_windows` from the time ring: batch row ``r`` holds window ``next + r`` = ``(j, a)``, fiber start
     ``fs[a]``, time start ``j * st`` (``tend`` for the end-aligned index), columns taken ``mod R``; rows from
-    ``avail`` on are zeros.  Returns (bf16 NHWC-8 batch, zero labels)."""
+    ``avail`` on are zeros.  Returns (bf16 NHWC-8 batch, zero labels).
+
+    ``sel`` / ``count`` / ``cursor`` (together; :func:`live_select`, :func:`live_gate_state`): row ``r`` holds window
+    ``sel[cursor * B + r]`` while that entry is below ``count``, zeros beyond."""
     fs = _starts(fs, ring.device)
     d = _live_args(ring, state, fs.numel(), st, window[1])
     g, out, lab = _gather_out(ring.device, fs, window, B, taps, off, lab_w)
     d.update(g)
+    d.update(selection_args(sel, count, None, cursor, live=True))
     lib().gather_windows_ring(stream(), d)
     return out, lab
 
 
 def live_probs(src: torch.Tensor, table: torch.Tensor, state: torch.Tensor, nf: int, jcap: int,
-               ncls: Optional[Sequence[int]] = None) -> torch.Tensor:
+               ncls: Optional[Sequence[int]] = None, sel: Optional[torch.Tensor] = None,
+               count: Optional[torch.Tensor] = None, cursor: Optional[torch.Tensor] = None) -> torch.Tensor:
     """:func:`window_probs` for the live numbering: batch row ``r`` is window ``next + r`` = ``(j, a)`` and goes to
     row ``(j mod jcap) * nf + a`` of the ring table ``table`` [>= jcap * nf, K] (in place); rows from ``avail`` on are
-    skipped.  The launch then advances ``next`` by the number of valid rows."""
+    skipped.  The launch then advances ``next`` by the number of valid rows.
+
+    ``sel`` / ``count`` / ``cursor`` (together): batch row ``r`` is window ``sel[cursor * B + r]`` while that entry
+    is below the count, and the table is the gated one, [>= jcap * nf, K + 1] -- columns ``0 .. K - 1`` the
+    probabilities, column ``K`` 1.0, "evaluated".  The launch then advances the cursor by one."""
     _check(table, torch.float32)
-    _check(state, torch.int64)
-    if state.numel() != LIVE_NSTATE:
-        raise ValueError(f"state must hold {LIVE_NSTATE} int64 scalars (live_state)")
-    N, K = table.shape
+    s = selection_args(sel, count, None, cursor, live=True)
+    N, pitch = table.shape
     if jcap < 1 or nf < 1 or N < jcap * nf:
         raise ValueError(f"a table of {N} rows is below jcap * nf = {jcap * nf}")
-    _, d = _prob_source(src, K, ncls)
-    d.update({"state": ptr(state), "nf": int(nf), "table": ptr(table), "nrows": N, "Jcap": int(jcap)})
+    _, d = _prob_source(src, pitch - int(bool(s)), ncls)
+    d.update(s)
+    d.update({"state": _live_scalars(state), "nf": int(nf), "table": ptr(table), "nrows": N, "pitch": pitch,
+              "Jcap": int(jcap)})
     lib().live_probs(stream(), d)
     return table
 
 
 # ---- the activity gate of a growing recording (csrc/live_gate.hip) ----------------------------------------------
 # Three rings of jcap time indices -- the windows' powers, their noise floors and their flags -- at row
-# (j mod jcap) * nf + a like the ring table, and a selection (sel, count, cursor) the captured step's rows are
-# numbered by.  Every launch works on the new window numbers [n0, n1): whole time indices, at most jcap of them.
+# (j mod jcap) * nf + a like the ring table, and a selection (sel, count, cursor) that gather_windows_ring and
+# live_probs take to number the captured step's rows.  Every launch works on the new window numbers [n0, n1): whole
+# time indices, at most jcap of them.
 MAX_FLOOR_HISTORY = 1024  # running_floor keeps a column's trailing powers in LDS
 
 
@@ -1048,14 +1057,6 @@ def _gate_rings(nf: int, jcap: int, n0: int, n1: int, **rings) -> dict:
             raise ValueError(f"the {k} ring must hold jcap * nf = {jcap * nf} entries")
         d[k] = ptr(t)
     return d
-
-
-def _gate_selection(state: torch.Tensor, sel: torch.Tensor, count: torch.Tensor, cursor: torch.Tensor) -> dict:
-    for t in (state, sel, count, cursor):
-        _check(t, torch.int64)
-    if state.numel() != LIVE_NSTATE or count.numel() != 1 or cursor.numel() != 1 or sel.dim() != 1:
-        raise ValueError("state must be live_state, count / cursor one number each, sel an int64 vector")
-    return {"state": ptr(state), "sel": ptr(sel), "cap": sel.numel(), "count": ptr(count), "cursor": ptr(cursor)}
 
 
 def ring_window_power(ring: torch.Tensor, state: torch.Tensor, fs, st: int, window: Tuple[int, int],
@@ -1098,7 +1099,8 @@ def live_select(power: torch.Tensor, floor: torch.Tensor, active: torch.Tensor, 
     cursor to 0 and ``state[LIVE_NEXT]`` to ``n1``."""
     _check(table, torch.float32)
     d = _gate_rings(nf, jcap, n0, n1, power=power, floor=floor, active=active)
-    d.update(_gate_selection(state, sel, count, cursor))
+    d.update(selection_args(sel, count, None, cursor, live=True))
+    d["state"] = _live_scalars(state)
     if table.dim() != 2 or table.shape[0] < jcap * nf:
         raise ValueError(f"a table of {tuple(table.shape)} is below jcap * nf = {jcap * nf} rows")
     if sel.numel() < n1 - n0:
@@ -1107,38 +1109,6 @@ def live_select(power: torch.Tensor, floor: torch.Tensor, active: torch.Tensor, 
     d.update({"ratio": gate_ratio(gate_db), "table": ptr(table), "nrows": table.shape[0], "pitch": table.shape[1],
               "offs": ptr(offs), "noffs": offs.numel()})
     lib().live_select(stream(), d)
-
-
-def gather_windows_ring_sel(ring: torch.Tensor, state: torch.Tensor, fs, st: int, window: Tuple[int, int], B: int,
-                            sel: torch.Tensor, count: torch.Tensor, cursor: torch.Tensor, taps: int = 0,
-                            off: int = 0, lab_w: int = 2):
-    """:func:`gather_windows_ring` with the batch rows numbered by a live selection: row ``r`` holds window
-    ``sel[cursor * B + r]`` while that entry is below ``count`` (:func:`live_gate_state`), zeros beyond."""
-    fs = _starts(fs, ring.device)
-    d = _live_args(ring, state, fs.numel(), st, window[1])
-    g, out, lab = _gather_out(ring.device, fs, window, B, taps, off, lab_w)
-    d.update(g)
-    d.update(_gate_selection(state, sel, count, cursor))
-    d["Jcap"] = 1  # (the gather touches no ring of the gate)
-    lib().gather_windows_ring_sel(stream(), d)
-    return out, lab
-
-
-def live_probs_sel(src: torch.Tensor, table: torch.Tensor, state: torch.Tensor, sel: torch.Tensor,
-                   count: torch.Tensor, cursor: torch.Tensor, nf: int, jcap: int, ncls: Optional[Sequence[int]] = None) -> torch.Tensor:
-    """:func:`live_probs` over a live selection into the gated ring table ``table`` [>= jcap * nf, K + 1] (in place):
-    batch row ``r`` is window ``sel[cursor * B + r]`` = ``(j, a)`` while that entry is below the count and goes to row
-    ``(j mod jcap) * nf + a`` -- columns ``0 .. K - 1`` the probabilities, column ``K`` 1.0, "evaluated".  The launch
-    then advances the cursor by one."""
-    _check(table, torch.float32)
-    N, pitch = table.shape
-    if jcap < 1 or nf < 1 or N < jcap * nf:
-        raise ValueError(f"a table of {N} rows is below jcap * nf = {jcap * nf}")
-    _, d = _prob_source(src, pitch - 1, ncls)
-    d.update(_gate_selection(state, sel, count, cursor))
-    d.update({"nf": int(nf), "table": ptr(table), "nrows": N, "pitch": pitch, "Jcap": int(jcap)})
-    lib().live_probs_sel(stream(), d)
-    return table
 
 
 def live_map(table: torch.Tensor, fs, F: int, Wf: int, cf: int, jcap: int, jlo, wt) -> torch.Tensor:

@@ -204,7 +204,8 @@ def test_selected_ring_gather_matches_linear_gather(R, C, taps, off):
     count.fill_(6)  # no multiple of B
     for cur, valid in ((0, 4), (1, 2), (2, 0)):
         cursor.fill_(cur)
-        out, lab = HF.gather_windows_ring_sel(ring, state, fs, ST, WIN, B, sel, count, cursor, taps=taps, off=off)
+        out, lab = HF.gather_windows_ring(ring, state, fs, ST, WIN, B, taps=taps, off=off, sel=sel, count=count,
+                                          cursor=cursor)
         rows = [(w % NF) * nt + w // NF for w in order[cur * B:cur * B + valid]] + [-1] * (B - valid)
         ref, _ = HF.gather_windows(full, fs, ts, WIN, B, idx=torch.tensor(rows, device="cuda"), taps=taps, off=off)
         assert not torch.isnan(out.float()).any()
@@ -251,7 +252,7 @@ def test_live_probs_sel_fills_the_gated_table(form):
                 logp[0] = torch.log_softmax(3 * torch.randn(B, 16, generator=g), 1)
                 logp[1, :, :2] = torch.log_softmax(3 * torch.randn(B, 2, generator=g), 1)
                 src, ncls = logp.cuda(), [16, 2]
-            HF.live_probs_sel(src, table, state, sel, count, cursor, NF, jcap, ncls=ncls)
+            HF.live_probs(src, table, state, NF, jcap, ncls=ncls, sel=sel, count=count, cursor=cursor)
             assert cursor.item() == cur + 1
             batch = chosen[cur * B:(cur + 1) * B]
             rows = [w - n0 for w in batch] + [-1] * (B - len(batch))  # row (j mod 2) * nf + a = n - n0
@@ -297,6 +298,16 @@ def test_launchers_refuse_bad_arguments():
     pr = {"state": ptr(state), "B": B, "nf": NF, "src": ptr(src), "softmax": 1, "K": K, "table": ptr(table),
           "nrows": n, "pitch": K + 1, "Jcap": jcap, "sel": ptr(sel), "cap": n, "count": ptr(count),
           "cursor": ptr(cursor)}
+    # the same launchers without a selection, and the resident recording's two (3 x 2 windows of 5 x 7)
+    none = dict(sel=0, count=0, cursor=0, cap=0)
+    rec = torch.zeros(1, F_, 16, device="cuda")
+    ts_d = torch.tensor([0, 9], dtype=torch.int32, device="cuda")
+    idx = torch.zeros(B, dtype=torch.int64, device="cuda")
+    res = {"rec": ptr(rec), "fs": ptr(fs_d), "ts": ptr(ts_d), "C": 1, "F": F_, "T": 16, "nf": NF, "nt": 2, "B": B,
+           "Wf": 5, "Wt": 7, "lo": 0, "hi": 2 * NF, "cursor": ptr(cursor), "sel": ptr(sel), "cap": n,
+           "count": ptr(count)}
+    wg = dict(res, taps=3, off=1, out=ptr(out), lab_out=ptr(lab), lab_w=2)
+    wp = dict(res, src=ptr(src), softmax=1, K=K, probs=ptr(table), nprobs=n)
     bad = [
         (lib().ring_window_power, dict(pw, power=0)),
         (lib().ring_window_power, dict(pw, ring=0)),
@@ -322,18 +333,30 @@ def test_launchers_refuse_bad_arguments():
         (lib().live_select, dict(se, noffs=0)),
         (lib().live_select, dict(se, nrows=n - 1)),
         (lib().live_select, dict(se, pitch=0)),
-        (lib().gather_windows_ring_sel, dict(ga, sel=0)),
-        (lib().gather_windows_ring_sel, dict(ga, count=0)),
-        (lib().gather_windows_ring_sel, dict(ga, cursor=0)),
-        (lib().gather_windows_ring_sel, dict(ga, out=0)),
-        (lib().gather_windows_ring_sel, dict(ga, R=7)),
-        (lib().live_probs_sel, dict(pr, pitch=K)),                 # the gated table has K + 1 columns
-        (lib().live_probs_sel, dict(pr, pitch=K + 2)),
-        (lib().live_probs_sel, dict(pr, table=0)),
-        (lib().live_probs_sel, dict(pr, nrows=n - 1)),
-        (lib().live_probs_sel, dict(pr, sel=0)),
-        (lib().live_probs_sel, dict(pr, count=0)),
+        (lib().gather_windows_ring, dict(ga, sel=0)),
+        (lib().gather_windows_ring, dict(ga, count=0)),
+        (lib().gather_windows_ring, dict(ga, cursor=0)),
+        (lib().gather_windows_ring, dict(ga, out=0)),
+        (lib().gather_windows_ring, dict(ga, R=7)),
+        (lib().gather_windows_ring, dict(ga, **dict(none, sel=ptr(sel), cap=n))),   # each of the three alone
+        (lib().gather_windows_ring, dict(ga, **dict(none, count=ptr(count)))),
+        (lib().gather_windows_ring, dict(ga, **dict(none, cursor=ptr(cursor)))),
+        (lib().live_probs, dict(pr, pitch=K)),                     # the gated table has K + 1 columns
+        (lib().live_probs, dict(pr, pitch=K + 2)),
+        (lib().live_probs, dict(pr, table=0)),
+        (lib().live_probs, dict(pr, nrows=n - 1)),
+        (lib().live_probs, dict(pr, sel=0)),
+        (lib().live_probs, dict(pr, count=0)),
+        (lib().live_probs, dict(pr, **none)),                      # no selection: the table has K columns
     ]
+    for fn, d in ((lib().gather_windows, wg), (lib().window_probs, wp)):
+        bad += [
+            (fn, dict(d, count=0)),                                # sel without count
+            (fn, dict(d, sel=0)),                                  # count without sel
+            (fn, dict(d, idx=ptr(idx))),                           # a selection with idx set, beside the cursor
+            (fn, dict(d, idx=ptr(idx), cursor=0)),                 # and in its place
+            (fn, dict(d, cursor=0)),                               # a selection with a null cursor
+        ]
     for fn, d in bad:
         with pytest.raises(RuntimeError, match="rc=-2"):
             fn(stream(), d)
