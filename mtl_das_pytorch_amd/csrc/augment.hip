@@ -12,9 +12,13 @@
 //   so a 7-tap pixel costs 3/4 of a Philox call (one pixel per thread would cost 2.5: every quad recomputed by the
 //   ten pixels whose taps reach it).  The noise depends on (seed, draw, dataset row, c, h, w) only -- not on the
 //   batch position or the launch geometry.  The levels, the draw number and the power table are device values.
+//   The arguments are the clean gather's GatherArgs plus NoiseArgs; the schedule row, the clear, the label gather and
+//   the limits both launchers share are stem_gather.h's.  The tap-packed store stays here (store_packed): it reads a
+//   thread's 16-row register array, not the column.
 // noise_advance: draw += 1 by one thread, launched after the gather (whose blocks all read the draw).
 #include "kernels.h"
 #include "philox.h"
+#include "stem_gather.h"
 
 namespace mda {
 
@@ -91,16 +95,13 @@ DEV void store_packed(const float* Y, int taps, int rows, bf16_t* __restrict__ o
 // One thread per (batch row, vertical quad q, column w), threads along w.  The 256 quads of a block belong to few
 // batch rows (two at the models' image sizes): their sigmas -- one Philox call for the SNR draw, exp10f, sqrtf -- are
 // computed once per block into LDS.
-__global__ __launch_bounds__(256) void gather_batch_noise_kernel(
-    const float* __restrict__ X, const int64_t* __restrict__ idx, const int64_t* __restrict__ lab, int lab_w,
-    bf16_t* __restrict__ out, int64_t* __restrict__ lab_out, int B, int Cin, int H, int W, int taps, int off,
-    ZeroRanges zero, const int64_t* __restrict__ cursor, int nrows, NoiseArgs nz) {
-  if (cursor) idx += (*cursor % nrows) * (int64_t)B;
-  {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x, nt = (int64_t)gridDim.x * 256;
-    for (int r = 0; r < zero.n; ++r)
-      for (int64_t i = t; i < zero.n16[r]; i += nt) zero.p[r][i] = make_uint4(0, 0, 0, 0);
-  }
+__global__ __launch_bounds__(256) void gather_batch_noise_kernel(GatherArgs a, NoiseArgs nz) {
+  // (read before the clear, with the kernel's first argument loads: see gather_batch_kernel)
+  const float* __restrict__ X = a.X;
+  bf16_t* __restrict__ out = a.out;
+  const int B = a.B, Cin = a.Cin, H = a.H, W = a.W, taps = a.taps, off = a.off;
+  const int64_t* __restrict__ idx = schedule_row(a);
+  clear_ranges(a.zero);
   const int HW = H * W;
   const int QW = ((H + 3) >> 2) * W;  // quads of one sample
   const int64_t M = (int64_t)B * QW;  // < 2^31 (the launcher checks B * H * W)
@@ -189,11 +190,7 @@ __global__ __launch_bounds__(256) void gather_batch_noise_kernel(
         if (i < rows) store8(o + (int64_t)i * W * 8, v[i]);
     }
   }
-  if (blockIdx.x == 0)
-    for (int i = threadIdx.x; i < B * lab_w; i += 256) {
-      const int b = i / lab_w, k = i - b * lab_w;
-      lab_out[i] = lab[idx[b] * lab_w + k];
-    }
+  gather_labels(a, idx);
 }
 
 __global__ void noise_advance_kernel(int64_t* draw) { *draw += 1; }
@@ -206,18 +203,13 @@ int launch_sample_power(const float* X, float* power, int64_t planes, int HW, hi
   return (int)hipGetLastError();
 }
 
-int launch_gather_batch_noise(const float* X, const int64_t* idx, const int64_t* lab, int lab_w, bf16_t* out,
-                              int64_t* lab_out, int B, int Cin, int H, int W, int taps, int off,
-                              const ZeroRanges& zero, const int64_t* cursor, int nrows, const NoiseArgs& noise,
-                              hipStream_t st) {
-  if (Cin > 8 || taps > 8 || (taps > 0 && Cin != 1) || (int64_t)B * H * W >= (1ll << 31)) return -2;
+int launch_gather_batch_noise(const GatherArgs& a, const NoiseArgs& noise, hipStream_t st) {
+  if (!gather_args_ok(a)) return -2;  // (B, Cin >= 1: the block's sigma table has at least one entry)
   if (!noise.power || !noise.snr || !noise.draw || noise.stream < 0 || noise.stream > 255) return -2;
-  if (B < 1 || Cin < 1 || H < 1 || W < 1 || taps < 0) return -2;  // (the block's sigma table: at least one entry)
-  if (taps > 0 && (off < 0 || off > 7)) return -2;  // the 16 rows a thread holds reach the taps (and the own rows)
-  const int64_t M = (int64_t)B * ((H + 3) / 4) * W;  // one thread per vertical quad of pixels
+  if (a.taps > 0 && (a.off < 0 || a.off > 7)) return -2;  // the 16 rows a thread holds reach the taps (and the own rows)
+  const int64_t M = (int64_t)a.B * ((a.H + 3) / 4) * a.W;  // one thread per vertical quad of pixels
   int blocks = (int)std::min<int64_t>((M + 255) / 256, 65535);
-  hipLaunchKernelGGL(gather_batch_noise_kernel, dim3(blocks), dim3(256), 0, st, X, idx, lab, lab_w, out, lab_out, B, Cin,
-                     H, W, taps, off, zero, cursor, nrows, noise);
+  hipLaunchKernelGGL(gather_batch_noise_kernel, dim3(blocks), dim3(256), 0, st, a, noise);
   return (int)hipGetLastError();
 }
 

@@ -328,10 +328,10 @@ void cls_head(int64_t stream, py::dict d) {
   check(launch_cls_head(a, P<int64_t>(d, "seed"), S(stream)), "cls_head");
 }
 
-void gather_batch(int64_t X, int64_t idx, int64_t lab, int lab_w, int64_t out, int64_t lab_out, int B, int Cin, int H,
-                  int W, int64_t stream, int taps, int off, py::list zero, int64_t cursor, int nrows) {
-  if (cursor && nrows <= 0) throw std::runtime_error("gather_batch: a schedule cursor needs its row count");
+// the up to 4 (pointer, bytes) regions a gather launch clears
+ZeroRanges parse_zero(const py::dict& d) {
   ZeroRanges z{};
+  py::list zero = d.contains("zero") ? d["zero"].cast<py::list>() : py::list();
   if (zero.size() > 4) throw std::runtime_error("gather_batch: at most 4 zero ranges");
   for (size_t i = 0; i < zero.size(); ++i) {
     auto t = zero[i].cast<py::tuple>();
@@ -341,42 +341,39 @@ void gather_batch(int64_t X, int64_t idx, int64_t lab, int lab_w, int64_t out, i
     z.n16[i] = bytes / 16;
   }
   z.n = (int)zero.size();
-  check(launch_gather_batch(reinterpret_cast<const float*>(X), reinterpret_cast<const int64_t*>(idx),
-                            reinterpret_cast<const int64_t*>(lab), lab_w, reinterpret_cast<bf16_t*>(out),
-                            reinterpret_cast<int64_t*>(lab_out), B, Cin, H, W, taps, off, z,
-                            reinterpret_cast<const int64_t*>(static_cast<intptr_t>(cursor)), nrows, S(stream)),
-        "gather_batch");
+  return z;
 }
 
-// gather_batch with SNR noise (augment.hip): the gather's arguments and the noise inputs in one dict
-void gather_batch_noise(int64_t stream, py::dict d) {
-  const int64_t cursor = I(d, "cursor");
-  const int nrows = (int)I(d, "nrows");
-  if (cursor && nrows <= 0) throw std::runtime_error("gather_batch_noise: a schedule cursor needs its row count");
-  ZeroRanges z{};
-  py::list zero = d.contains("zero") ? d["zero"].cast<py::list>() : py::list();
-  if (zero.size() > 4) throw std::runtime_error("gather_batch_noise: at most 4 zero ranges");
-  for (size_t i = 0; i < zero.size(); ++i) {
-    auto t = zero[i].cast<py::tuple>();
-    const int64_t ptr = t[0].cast<int64_t>(), bytes = t[1].cast<int64_t>();
-    if (ptr % 16 || bytes % 16 || bytes < 0)
-      throw std::runtime_error("gather_batch_noise: zero range not 16-byte aligned");
-    z.p[i] = reinterpret_cast<uint4*>(static_cast<intptr_t>(ptr));
-    z.n16[i] = bytes / 16;
-  }
-  z.n = (int)zero.size();
+GatherArgs parse_gather(const py::dict& d) {
+  GatherArgs a{};
+  a.X = P<const float>(d, "X"); a.idx = P<const int64_t>(d, "idx"); a.lab = P<const int64_t>(d, "lab");
+  a.lab_w = (int)I(d, "lab_w"); a.out = P<bf16_t>(d, "out"); a.lab_out = P<int64_t>(d, "lab_out");
+  a.B = (int)I(d, "B"); a.Cin = (int)I(d, "Cin"); a.H = (int)I(d, "H"); a.W = (int)I(d, "W");
+  a.taps = (int)I(d, "taps"); a.off = (int)I(d, "off");
+  a.zero = parse_zero(d);
+  a.cursor = P<const int64_t>(d, "cursor"); a.nrows = (int)I(d, "nrows");
+  if (a.cursor && a.nrows <= 0) throw std::runtime_error("gather_batch: a schedule cursor needs its row count");
+  return a;
+}
+
+NoiseArgs parse_noise(const py::dict& d) {
   NoiseArgs nz{};
   nz.power = P<const float>(d, "power"); nz.snr = P<const float>(d, "snr"); nz.draw = P<const int64_t>(d, "draw");
   // the 64-bit seed as two 32-bit words (a Python int above 2^63 does not fit the dict's int64 values)
   nz.seed = ((uint64_t)(uint32_t)I(d, "seed_hi") << 32) | (uint64_t)(uint32_t)I(d, "seed_lo");
   nz.stream = (int)I(d, "noise_stream");
   nz.dbg = P<float>(d, "dbg");
-  check(launch_gather_batch_noise(P<const float>(d, "X"), P<const int64_t>(d, "idx"), P<const int64_t>(d, "lab"),
-                                  (int)I(d, "lab_w"), P<bf16_t>(d, "out"), P<int64_t>(d, "lab_out"), (int)I(d, "B"),
-                                  (int)I(d, "Cin"), (int)I(d, "H"), (int)I(d, "W"), (int)I(d, "taps"),
-                                  (int)I(d, "off"), z, reinterpret_cast<const int64_t*>(static_cast<intptr_t>(cursor)),
-                                  nrows, nz, S(stream)),
-        "gather_batch_noise");
+  return nz;
+}
+
+// The batch gather (misc.hip); with a nested "noise" dict the gather with SNR noise (augment.hip), whose launcher
+// refuses a null noise input: a "noise" dict never runs the clean kernel.
+void gather_batch(int64_t stream, py::dict d) {
+  const GatherArgs a = parse_gather(d);
+  if (d.contains("noise") && !d["noise"].is_none())
+    check(launch_gather_batch_noise(a, parse_noise(d["noise"].cast<py::dict>()), S(stream)), "gather_batch_noise");
+  else
+    check(launch_gather_batch(a, S(stream)), "gather_batch");
 }
 
 void sample_power(int64_t X, int64_t power, int64_t planes, int HW, int64_t stream) {
@@ -643,11 +640,7 @@ PYBIND11_MODULE(_mda_hip, m) {
   m.def("tail_bwd", &tail_bwd);
   m.def("mtl_head", &mtl_head);
   m.def("cls_head", &cls_head);
-  m.def("gather_batch", &gather_batch, py::arg("X"), py::arg("idx"), py::arg("lab"), py::arg("lab_w"), py::arg("out"),
-        py::arg("lab_out"), py::arg("B"), py::arg("Cin"), py::arg("H"), py::arg("W"), py::arg("stream"),
-        py::arg("taps") = 0, py::arg("off") = 0, py::arg("zero") = py::list(), py::arg("cursor") = 0,
-        py::arg("nrows") = 0);
-  m.def("gather_batch_noise", &gather_batch_noise);
+  m.def("gather_batch", &gather_batch);
   m.def("sample_power", &sample_power);
   m.def("noise_advance", &noise_advance);
   m.def("pool3", &pool3);

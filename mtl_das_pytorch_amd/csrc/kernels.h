@@ -314,10 +314,24 @@ struct ZeroRanges {  // up to 4 16-byte-aligned regions a launch zeroes (gather_
   int64_t n16[4];     // 16-byte units
   int n;
 };
-int launch_gather_batch(const float* X, const int64_t* idx, const int64_t* lab, int lab_w, bf16_t* out,
-                        int64_t* lab_out, int B, int Cin, int H, int W, int taps, int off, const ZeroRanges& zero,
-                        const int64_t* cursor, int nrows,
-                        hipStream_t st);
+// The batch gather's arguments, the clean kernel's (misc.hip) and the noisy one's (augment.hip).  What both kernels
+// and the window gathers share -- the schedule row, the clear, the label gather, the stem pixel and the limits
+// gather_args_ok -- is in stem_gather.h.
+struct GatherArgs {
+  const float* X;         // resident dataset [N][Cin][H][W] fp32
+  const int64_t* idx;     // [B] dataset rows, or with cursor a [nrows][B] schedule
+  const int64_t* lab;     // [N][lab_w]
+  int lab_w;
+  bf16_t* out;            // [B][H][W][8]
+  int64_t* lab_out;       // [B][lab_w]
+  int B, Cin, H, W;
+  int taps, off;          // vertical tap packing of a 1-channel stem (0: Cin real channels padded to 8)
+  ZeroRanges zero;
+  const int64_t* cursor;  // optional: the step gathers schedule row *cursor mod nrows
+  int nrows;
+};
+// -2 on gather_args_ok
+int launch_gather_batch(const GatherArgs& a, hipStream_t st);
 // augment.hip: SNR noise injected by the batch gather (definition: data/noise.py).  Every level a run may change
 // is a device value, so a captured step never needs re-capture.
 struct NoiseArgs {
@@ -329,11 +343,9 @@ struct NoiseArgs {
   float* dbg;            // test hook (null in the engine): the unrounded fp32 noisy values [B][Cin][H][W]
 };
 int launch_sample_power(const float* X, float* power, int64_t planes, int HW, hipStream_t st);
-// launch_gather_batch with bf16(x + sigma * g) for every real element; -2 on its limits or a null noise input
-int launch_gather_batch_noise(const float* X, const int64_t* idx, const int64_t* lab, int lab_w, bf16_t* out,
-                              int64_t* lab_out, int B, int Cin, int H, int W, int taps, int off,
-                              const ZeroRanges& zero, const int64_t* cursor, int nrows, const NoiseArgs& noise,
-                              hipStream_t st);
+// launch_gather_batch with bf16(x + sigma * g) for every real element; -2 on gather_args_ok, a null noise input, a
+// stream id outside 0..255 or a tap offset outside 0..7
+int launch_gather_batch_noise(const GatherArgs& a, const NoiseArgs& noise, hipStream_t st);
 int launch_noise_advance(int64_t* draw, hipStream_t st);
 int launch_pool3(int is_max, int backward, const PoolArgs& a, hipStream_t st);
 // window.hip / live.hip: sliding-window inference over a resident and over a growing recording.  What the two share

@@ -3,72 +3,47 @@
 // gather_batch: the on-device replacement of the reference's host data path (DataLoader collate of
 //   loadmat'd arrays + pageable .cuda() copies, utils.py:264-266,351-353): picks the batch rows of an
 //   HBM-resident fp32 NCHW dataset by index, converts to bf16 NHWC with the channel dim zero-padded to
-//   8 (so the 1-channel stem runs on the generic MFMA implicit-GEMM path) and gathers the labels.
+//   8 (so the 1-channel stem runs on the generic MFMA implicit-GEMM path) and gathers the labels.  Its arguments
+//   are GatherArgs (kernels.h); every piece it shares with the other writers of the stem's input is in stem_gather.h.
 // Inception pools (model C, torchvision semantics used by modelC_multiClassifier.py):
 //   maxpool 3x3/s2 (valid) and avgpool 3x3/s1/p1 (count_include_pad=True), forward and backward; the
 //   backward passes are written in gather form (each input pixel sums the windows that cover it and,
 //   for max, recomputes the first-max argmax), so they are deterministic and need no index tensors.
 #include "kernels.h"
+#include "stem_gather.h"
 
 namespace mda {
 
-// taps > 0 (single-channel input): vertical tap packing for the stem conv -- channel j of pixel (h, w)
-// holds x[h - off + j][w] (zero outside the image, j < taps), so a KHxKW stem over 1 channel runs as a
-// 1xKW conv over KH real channels (engine/core.py stem_pack_geom) instead of wasting 7/8 of its K on
-// zero padding channels.
-// zero: the arena's zeroed regions (BN statistic replicas, backward workspaces) cleared by the same launch
-// at the start of a training step -- one dependent launch instead of a gather plus a fill per dtype.
-__global__ __launch_bounds__(256) void gather_batch_kernel(const float* __restrict__ X, const int64_t* __restrict__ idx,
-                                                           const int64_t* __restrict__ lab, int lab_w,
-                                                           bf16_t* __restrict__ out, int64_t* __restrict__ lab_out,
-                                                           int B, int Cin, int H, int W, int taps, int off,
-                                                           ZeroRanges zero, const int64_t* __restrict__ cursor,
-                                                           int nrows) {
-  // batch-index schedule (cursor set): this step's indices are row (*cursor mod nrows) of a [nrows][B] table;
-  // the optimizer's step-counter kernel advances the cursor at the end of the step, so no host copy of the
-  // indices precedes each replay
-  if (cursor) idx += (*cursor % nrows) * (int64_t)B;
-  {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x, nt = (int64_t)gridDim.x * 256;
-    for (int r = 0; r < zero.n; ++r)
-      for (int64_t i = t; i < zero.n16[r]; i += nt) zero.p[r][i] = make_uint4(0, 0, 0, 0);
-  }
+// One pixel per thread.  The schedule row, the clear, the stem pixel (tap packing or channel padding) and the label
+// gather are stem_gather.h's, shared with the noisy gather (augment.hip) and the window gathers.
+__global__ __launch_bounds__(256) void gather_batch_kernel(GatherArgs a) {
+  // the pixel loop's fields are read here, with the kernel's first argument loads: a field of the by-value struct is
+  // loaded where the code first reads it, and after the clear that is one more serial round trip per field group
+  const float* __restrict__ X = a.X;
+  bf16_t* __restrict__ out = a.out;
+  const int B = a.B, Cin = a.Cin, H = a.H, W = a.W, taps = a.taps, off = a.off;
+  const int64_t* __restrict__ idx = schedule_row(a);
+  clear_ranges(a.zero);
   const int64_t M = (int64_t)B * H * W;
   const int HW = H * W;
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < M; p += (int64_t)gridDim.x * 256) {
-    const int b = (int)p / HW;  // M < 2^31 (checked by the launcher)
+    const int b = (int)p / HW;  // M < 2^31 (gather_args_ok)
     const int r = (int)p - b * HW;
     const int64_t src = idx[b];
     float v[8];
-    if (taps > 0) {
-      const int h = r / W;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int hh = h - off + j;
-        v[j] = (j < taps && hh >= 0 && hh < H) ? X[src * (int64_t)H * W + r + (hh - h) * W] : 0.f;
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < 8; ++c) v[c] = c < Cin ? X[(src * Cin + c) * (int64_t)H * W + r] : 0.f;
-    }
+    if (taps > 0) stem_taps(X + src * (int64_t)HW + r, W, r / W, H, taps, off, v);
+    else stem_channels(X + src * Cin * (int64_t)HW + r, HW, Cin, v);
     store8(out + p * 8, v);
   }
-  if (blockIdx.x == 0)
-    for (int i = threadIdx.x; i < B * lab_w; i += 256) {
-      const int b = i / lab_w, k = i - b * lab_w;
-      lab_out[i] = lab[idx[b] * lab_w + k];
-    }
+  gather_labels(a, idx);
 }
 
-int launch_gather_batch(const float* X, const int64_t* idx, const int64_t* lab, int lab_w, bf16_t* out,
-                        int64_t* lab_out, int B, int Cin, int H, int W, int taps, int off, const ZeroRanges& zero,
-                        const int64_t* cursor, int nrows, hipStream_t st) {
-  if (Cin > 8 || taps > 8 || (taps > 0 && Cin != 1) || (int64_t)B * H * W >= (1ll << 31)) return -2;
-  const int64_t M = (int64_t)B * H * W;
+int launch_gather_batch(const GatherArgs& a, hipStream_t st) {
+  if (!gather_args_ok(a)) return -2;
+  const int64_t M = (int64_t)a.B * a.H * a.W;
   // one pixel per thread (no grid-stride second round: the idx -> X -> store chain is latency-bound)
   int blocks = (int)std::min<int64_t>((M + 255) / 256, 65535);
-  hipLaunchKernelGGL(gather_batch_kernel, dim3(blocks), dim3(256), 0, st, X, idx, lab, lab_w, out, lab_out, B, Cin, H, W,
-                     taps, off, zero, cursor, nrows);
+  hipLaunchKernelGGL(gather_batch_kernel, dim3(blocks), dim3(256), 0, st, a);
   return (int)hipGetLastError();
 }
 

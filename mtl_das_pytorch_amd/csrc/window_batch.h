@@ -3,7 +3,8 @@
 //
 //   * the gather body: the NHWC-8 pixel loop with the stem's tap packing and the window-edge padding, a template
 //     over two separate things: the numbering (which window number batch row b holds, or that it is padding) and
-//     the source (where window n starts, which column holds time t, base pointer and row pitch);
+//     the source (where window n starts, which column holds time t, base pointer and row pitch); the pixel itself
+//     -- 8 tap-packed channels of a column, or C channels padded to 8 -- is the batch gather's (stem_gather.h);
 //   * the selected numbering, the one both sources and both probability kernels use when the launch carries a
 //     Selection: entry cur * B + r of sel while below the count and the capacity;
 //   * the ring as a source (RingSource) and its table row, the window power body (a template over the source, so
@@ -19,6 +20,7 @@
 // kernel: their rounding is the kernel's.
 #pragma once
 #include "kernels.h"
+#include "stem_gather.h"
 
 namespace mda {
 
@@ -57,19 +59,9 @@ DEV void gather_windows_body(const WindowGeom& g, const Source& src, const Numbe
     int f0;
     typename Source::time_type t0;
     if (src.numbered(num(b), f0, t0) && f0 >= 0 && f0 + g.Wf <= g.F) {
-      const int64_t col = src.column(t0 + w);
-      if (g.taps > 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int hh = h - g.off + j;
-          if (j < g.taps && hh >= 0 && hh < g.Wf) v[j] = x[(int64_t)(f0 + hh) * pitch + col];
-        }
-      } else {
-        const int64_t at = (int64_t)(f0 + h) * pitch + col;
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-          if (c < g.C) v[c] = x[c * plane + at];
-      }
+      const float* at = x + (int64_t)(f0 + h) * pitch + src.column(t0 + w);  // the pixel's element of channel 0
+      if (g.taps > 0) stem_taps(at, pitch, h, g.Wf, g.taps, g.off, v);
+      else stem_channels(at, plane, g.C, v);
     }
     store8(out + p * 8, v);
   }

@@ -8,14 +8,14 @@ from typing import Callable, Dict, List, Optional
 
 import torch
 
-from ..ops.functional import LIVE_NSTATE, WGRAD_PATCH, WGRAD_TILES, noise_args, selection_args, wgrad_ktiles
+from ..ops.functional import LIVE_NSTATE, WGRAD_PATCH, WGRAD_TILES, gather_args, noise_args, selection_args, wgrad_ktiles
 from ..ops.hip import lib
 from .core import (GRAD_DT, Act, BNLayer, ConvLayer, P, build_optseg_table, build_wgfin_table, optimizer_segments,
                    pad_to)
 from .program import (COMM_STREAM, SPILL_STREAM, Launch, Phase, k_adam, k_step_inc, k_allreduce, k_ext_record, k_conv, k_gather, k_gather_windows, k_tail_bwd, k_tail_fwd,
                       k_tail_fwd_batched, k_wgfin, k_wgrad,
                       k_wgrad_batched, k_window_probs)
-from .program import NoiseSpec, k_gather_noise, k_noise_advance
+from .program import NoiseSpec, k_noise_advance
 from .program import k_gather_windows_ring, k_live_probs
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID, SIGMUL, ADD_RELU, POOL_RELU = range(6)
@@ -414,21 +414,21 @@ class LoweredProgram:
             if zero is None:
                 ph.add("clear", lambda st: self.arena.clear())
                 zero = []
+        nz = None
+        ph.keep = (X, labels, idx, cursor)
         if noise is not None:
             if tuple(noise.power.shape) != (X.shape[0], X.shape[1]):
                 raise ValueError("the noise power table does not belong to this dataset")
-            d = noise_args(noise.power, noise.snr, noise.draw, noise.seed, 0 if noise.train else 2)
-            d.update({"X": P(X), "idx": P(idx), "lab": P(labels), "lab_w": self.label_width, "out": P(self.x),
-                      "lab_out": P(self.labels), "B": self.B, "Cin": X.shape[1], "H": self.H0, "W": self.W0,
-                      "taps": self.stem_pack[0], "off": self.stem_pack[1], "zero": zero, "cursor": P(cursor),
-                      "nrows": idx.shape[0] if cursor is not None else 0})
-            ph.add("gather_noise", k_gather_noise, d)
-            if noise.train:
-                ph.add("noise_advance", k_noise_advance, noise.draw)
-            ph.keep = (X, labels, idx, cursor, noise.power, noise.snr, noise.draw)
-            return ph
-        ph.add("gather", k_gather, X, idx, labels, self.label_width, self.x, self.labels, self.B, X.shape[1], self.H0,
-               self.W0, *self.stem_pack, zero, cursor)
+            if any(t.device != X.device for t in (noise.power, noise.snr, noise.draw)):
+                raise ValueError("the noise tensors must live on the dataset's device")
+            nz = noise_args(noise.power, noise.snr, noise.draw, noise.seed, 0 if noise.train else 2)
+            ph.keep += (noise.power, noise.snr, noise.draw)
+        d = gather_args(X=X, labels=labels, lab_w=self.label_width, idx=idx, out=self.x, lab_out=self.labels, B=self.B,
+                        H=self.H0, W=self.W0, taps=self.stem_pack[0], off=self.stem_pack[1], zero=zero, cursor=cursor,
+                        noise=nz)
+        ph.add("gather" if nz is None else "gather_noise", k_gather, d)
+        if noise is not None and noise.train:
+            ph.add("noise_advance", k_noise_advance, noise.draw)
         return ph
 
     def _window_args(self, idx, cursor, lo: int, hi: int) -> dict:

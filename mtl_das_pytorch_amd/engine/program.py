@@ -388,12 +388,11 @@ def k_allreduce(fn, t, st):
     fn(t.t if hasattr(t, "bind") else t)  # arena LazyView -> its bound tensor
 
 
-def k_gather(X, idx, lab, lab_w, out, lab_out, B, Cin, H, W, taps, off, zero, cursor, st):
-    """``cursor``: None, or the device int64 cursor of a [nrows][B] batch-index schedule ``idx`` (StepRunner
-    set_index_schedule): the kernel gathers row cursor mod nrows."""
-    lib().gather_batch(X.data_ptr(), idx.data_ptr(), lab.data_ptr(), lab_w, out.data_ptr(), lab_out.data_ptr(),
-                       B, Cin, H, W, st, taps, off, zero, cursor.data_ptr() if cursor is not None else 0,
-                       idx.shape[0] if cursor is not None else 0)
+def k_gather(d, st):
+    """The batch gather (``d``: ops.functional.gather_args).  With a ``"cursor"`` the kernel gathers row cursor mod
+    nrows of a [nrows][B] batch-index schedule (StepRunner set_index_schedule); with a ``"noise"`` dict it is the
+    gather with SNR noise (csrc/augment.hip)."""
+    lib().gather_batch(st, d)
 
 
 class NoiseSpec:
@@ -405,11 +404,6 @@ class NoiseSpec:
 
     def __init__(self, power, snr, draw, seed: int, train: bool):
         self.power, self.snr, self.draw, self.seed, self.train = power, snr, draw, int(seed), bool(train)
-
-
-def k_gather_noise(d, st):
-    """The batch gather with SNR noise (csrc/augment.hip; ``d``: the gather's arguments and the noise inputs)."""
-    lib().gather_batch_noise(st, d)
 
 
 def k_noise_advance(draw, st):

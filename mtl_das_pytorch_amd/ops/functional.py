@@ -618,14 +618,47 @@ def pool3_backward(x: torch.Tensor, g: torch.Tensor, is_max: bool, am: Optional[
     return dx
 
 
-def gather_batch(X: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor):
-    """HBM-resident dataset rows -> (bf16 NHWC batch with C padded to 8, labels)."""
+def gather_args(*, X, labels, lab_w: int, idx, out, lab_out, B: int, H: int, W: int, taps: int = 0, off: int = 0,
+                zero=(), cursor=None, noise: Optional[dict] = None) -> dict:
+    """The launch dict of the batch gather as the binding reads it, the one builder behind :func:`gather_batch`,
+    :func:`gather_batch_noise` and the engine's gather phase.  The arguments are :func:`gather_batch`'s; ``out`` /
+    ``lab_out``: the [B, H, W, 8] bf16 and [B, lab_w] int64 tensors written; ``zero``: (pointer, bytes) pairs.
+    ``noise`` (:func:`noise_args`) is nested under ``"noise"``: the key selects the noisy kernel, absent the clean."""
+    d = {"X": ptr(X), "idx": ptr(idx), "lab": ptr(labels), "lab_w": lab_w, "out": ptr(out), "lab_out": ptr(lab_out),
+         "B": B, "Cin": X.shape[1], "H": H, "W": W, "taps": taps, "off": off, "zero": list(zero),
+         "cursor": ptr(cursor), "nrows": idx.shape[0] if cursor is not None else 0}
+    if noise is not None:
+        d["noise"] = noise
+    return d
+
+
+def gather_batch(X: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor, taps: int = 0, off: int = 0,
+                 zero: Sequence[torch.Tensor] = (), cursor: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None, noise: Optional[dict] = None):
+    """HBM-resident dataset rows -> (bf16 NHWC batch with C padded to 8, labels).  ``idx``: int64 [B], or with
+    ``cursor`` (a device int64 scalar) a [nrows, B] schedule whose row ``cursor`` mod nrows is gathered.  ``taps`` /
+    ``off``: the 1-channel stem's vertical tap packing.  ``zero``: up to 4 tensors the launch clears (16-byte aligned
+    and sized).  ``out``: the [B, H, W, 8] bf16 output to write.  ``noise``: :func:`noise_args` -- every real element
+    becomes ``bf16(x + sigma * g)`` (:func:`gather_batch_noise`)."""
+    _check(X, torch.float32)
+    _check(idx, torch.int64)
+    _check(labels, torch.int64)
     N, Cin, H, W = X.shape
-    B = idx.numel()
+    B = idx.shape[-1] if cursor is not None else idx.numel()
+    if cursor is not None:
+        _check(cursor, torch.int64)
+        if idx.dim() != 2:
+            raise ValueError("a cursor needs a [nrows, B] index schedule")
+    if out is None:
+        out = torch.empty(B, H, W, 8, device=X.device, dtype=torch.bfloat16)
+    _check(out, torch.bfloat16)
+    if out.numel() < B * H * W * 8:
+        raise ValueError("output too small")
     lw = labels.shape[1] if labels.dim() == 2 else 1
-    out = torch.empty(B, H, W, 8, device=X.device, dtype=torch.bfloat16)
     lab = torch.empty(B, lw, device=X.device, dtype=torch.int64)
-    lib().gather_batch(ptr(X), ptr(idx), ptr(labels), lw, ptr(out), ptr(lab), B, Cin, H, W, stream())
+    zero = [(z.data_ptr(), z.numel() * z.element_size()) for z in zero]
+    lib().gather_batch(stream(), gather_args(X=X, labels=labels, lab_w=lw, idx=idx, out=out, lab_out=lab, B=B, H=H, W=W,
+                                             taps=taps, off=off, zero=zero, cursor=cursor, noise=noise))
     return out, lab
 
 
@@ -642,11 +675,13 @@ def sample_power(X: torch.Tensor) -> torch.Tensor:
 
 
 def noise_args(power: torch.Tensor, snr: torch.Tensor, draw: torch.Tensor, seed: int, noise_stream: int) -> dict:
-    """The noise inputs of :func:`gather_batch_noise` as the binding reads them: the device power table [N, C], the
-    device (lo, hi) fp32 pair, the device int64 draw number, and the launch constants (seed, stream id)."""
-    _check(power, torch.float32)
-    _check(snr, torch.float32)
-    _check(draw, torch.int64)
+    """The noise inputs of the batch gather as the binding reads them, the ``"noise"`` dict nested in
+    :func:`gather_args`: the device power table [N, C], the device (lo, hi) fp32 pair, the device int64 draw number,
+    and the launch constants (seed, stream id).  The three tensors live where the dataset does (the callers check
+    that: a program lowers on the CPU too)."""
+    for t, dtype in ((power, torch.float32), (snr, torch.float32), (draw, torch.int64)):
+        if t.dtype != dtype or not t.is_contiguous():
+            raise TypeError(f"expected a contiguous {dtype} tensor, got {t.dtype}")
     if snr.numel() != 2 or draw.numel() != 1:
         raise ValueError("snr must hold (lo, hi) and draw one number")
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -660,40 +695,21 @@ def gather_batch_noise(X: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor,
                        out: Optional[torch.Tensor] = None, dbg: Optional[torch.Tensor] = None):
     """:func:`gather_batch` with SNR noise (data/noise.py): every real element is ``bf16(x + sigma * g)``, padding
     channels and out-of-image taps stay 0.  ``power``: :func:`sample_power` of ``X``; ``snr``: device fp32 (lo, hi);
-    ``draw``: device int64 scalar; ``noise_stream``: 0 training, 2 evaluation.  ``idx``: int64 [B], or with
-    ``cursor`` (a device int64 scalar) a [nrows, B] schedule whose row ``cursor`` mod nrows is gathered.  ``taps`` /
-    ``off``: the 1-channel stem's vertical tap packing.  ``zero``: up to 4 tensors the launch clears (16-byte aligned
-    and sized).  ``out``: the [B, H, W, 8] bf16 output to write; ``dbg``: an fp32 [B, Cin, H, W] tensor that
-    receives the unrounded noisy values (test hook).  Returns (out, labels)."""
-    _check(X, torch.float32)
-    _check(idx, torch.int64)
-    _check(labels, torch.int64)
+    ``draw``: device int64 scalar; ``noise_stream``: 0 training, 2 evaluation.  ``idx`` / ``cursor``, ``taps`` /
+    ``off``, ``zero`` and ``out``: :func:`gather_batch`'s.  ``dbg``: an fp32 [B, Cin, H, W] tensor that receives the
+    unrounded noisy values (test hook).  Returns (out, labels)."""
     N, Cin, H, W = X.shape
     if tuple(power.shape) != (N, Cin):
         raise ValueError(f"power table must be [{N}, {Cin}]")
-    B = idx.shape[-1] if cursor is not None else idx.numel()
-    if cursor is not None:
-        _check(cursor, torch.int64)
-        if idx.dim() != 2:
-            raise ValueError("a cursor needs a [nrows, B] index schedule")
-    lw = labels.shape[1] if labels.dim() == 2 else 1
-    if out is None:
-        out = torch.empty(B, H, W, 8, device=X.device, dtype=torch.bfloat16)
-    _check(out, torch.bfloat16)
-    if out.numel() < B * H * W * 8:
-        raise ValueError("output too small")
+    for t in (power, snr, draw):
+        _check(t)
+    d = noise_args(power, snr, draw, seed, noise_stream)
     if dbg is not None:
         _check(dbg, torch.float32)
-        if dbg.numel() < B * Cin * H * W:
+        if dbg.numel() < (idx.shape[-1] if cursor is not None else idx.numel()) * Cin * H * W:
             raise ValueError("dbg too small")
-    lab = torch.empty(B, lw, device=X.device, dtype=torch.int64)
-    d = noise_args(power, snr, draw, seed, noise_stream)
-    d.update({"X": ptr(X), "idx": ptr(idx), "lab": ptr(labels), "lab_w": lw, "out": ptr(out), "lab_out": ptr(lab),
-              "B": B, "Cin": Cin, "H": H, "W": W, "taps": taps, "off": off,
-              "zero": [(z.data_ptr(), z.numel() * z.element_size()) for z in zero],
-              "cursor": ptr(cursor), "nrows": idx.shape[0] if cursor is not None else 0, "dbg": ptr(dbg)})
-    lib().gather_batch_noise(stream(), d)
-    return out, lab
+        d["dbg"] = ptr(dbg)
+    return gather_batch(X, labels, idx, taps=taps, off=off, zero=zero, cursor=cursor, out=out, noise=d)
 
 
 def noise_advance(draw: torch.Tensor):

@@ -491,3 +491,43 @@ def test_stream_param_order_gives_model_c_side_stream_buckets():
         for q in f.order:
             if lo <= f.off(q) < hi:
                 assert all(s == a.stream and i <= i0 for s, i in writers.get(f.off(q), ())), q.shape
+
+
+def test_gather_phase_is_one_launch_of_one_dict():
+    """The gather phase adds one gather launch of one argument dict (ops.functional.gather_args): ``gather`` without
+    noise, ``gather_noise`` -- the same adapter, a nested ``"noise"`` dict -- with a NoiseSpec, followed by the draw
+    advance for a training spec only."""
+    from mtl_das_pytorch_amd.engine.program import NoiseSpec, k_gather, k_noise_advance
+    B, N = 4, 6
+    p = MTLProgram(MTL_Net(), B, "cpu")
+    X, lab = torch.zeros(N, 1, p.H0, p.W0), torch.zeros(N, 2, dtype=torch.int64)
+    idx, sched, cursor = torch.arange(B), torch.arange(3 * B).view(3, B) % N, torch.zeros(1, dtype=torch.int64)
+    power, snr, draw = torch.ones(N, 1), torch.tensor([0.0, 20.0]), torch.zeros(1, dtype=torch.int64)
+    seed = (5 << 32) | 9
+
+    ph = p.gather_phase(X, lab, idx)
+    assert [(l.name, l.fn) for l in ph.launches] == [("gather", k_gather)]
+    clean = ph.launches[0].d
+    assert ph.launches[0].args == (clean,) and "noise" not in clean
+    assert clean["nrows"] == 0 and clean["cursor"] == 0 and clean["idx"] == idx.data_ptr()
+    assert (clean["B"], clean["Cin"], clean["H"], clean["W"], clean["lab_w"]) == (B, 1, p.H0, p.W0, 2)
+    assert (clean["taps"], clean["off"]) == p.stem_pack and clean["out"] == p.x.data_ptr()
+    assert all(any(k is t for k in ph.keep) for t in (X, lab, idx))
+
+    ph = p.gather_phase(X, lab, idx, noise=NoiseSpec(power, snr, draw, seed, train=True))
+    assert [(l.name, l.fn) for l in ph.launches] == [("gather_noise", k_gather), ("noise_advance", k_noise_advance)]
+    noisy = ph.launches[0].d
+    assert noisy["noise"] == {"power": power.data_ptr(), "snr": snr.data_ptr(), "draw": draw.data_ptr(),
+                              "seed_lo": 9, "seed_hi": 5, "noise_stream": 0}
+    assert ph.launches[1].args == (draw,)
+    assert {k: v for k, v in noisy.items() if k != "noise"} == clean  # the gather fields, field by field
+    assert all(any(k is t for k in ph.keep) for t in (X, lab, idx, power, snr, draw))
+
+    ph = p.gather_phase(X, lab, idx, noise=NoiseSpec(power, snr, draw, seed, train=False))
+    assert [(l.name, l.fn) for l in ph.launches] == [("gather_noise", k_gather)]
+    assert ph.launches[0].d["noise"]["noise_stream"] == 2
+
+    for spec in (None, NoiseSpec(power, snr, draw, seed, train=True)):
+        d = p.gather_phase(X, lab, sched, cursor=cursor, noise=spec).launches[0].d
+        assert d["nrows"] == sched.shape[0] == 3 and d["cursor"] == cursor.data_ptr() and d["idx"] == sched.data_ptr()
+        assert d["B"] == B

@@ -49,26 +49,26 @@ class Gather:
         self.zero = torch.full((40,), 7.0, device="cuda")
 
     def args(self, sched):
+        """The launch dict (ops.functional.gather_args), writing this case's sentinel-followed buffers."""
+        from mtl_das_pytorch_amd.ops.functional import gather_args
         if sched:
             other = (self.unused * self.B)[:self.B]
             self.idx = torch.tensor([other, list(ROWS)]).cuda()
             self.cursor = torch.tensor([3]).cuda()
-            kw = {"cursor": self.cursor.data_ptr(), "nrows": 2}
         else:
-            self.idx = torch.tensor(ROWS).cuda()
-            kw = {}
-        pos = (self.dX.data_ptr(), self.idx.data_ptr(), self.dlab.data_ptr(), 2, self.out.data_ptr(),
-               self.lab_out.data_ptr(), self.B, self.Cin, H, W, _stream())
-        kw.update(taps=0, off=0, zero=[(self.zero.data_ptr() + 16, 32 * 4)])
-        return pos, kw
+            self.idx, self.cursor = torch.tensor(ROWS).cuda(), None
+        return gather_args(X=self.dX, labels=self.dlab, lab_w=2, idx=self.idx, out=self.out, lab_out=self.lab_out,
+                           B=self.B, H=H, W=W, taps=0, off=0, zero=[(self.zero.data_ptr() + 16, 32 * 4)],
+                           cursor=self.cursor)
 
 
 @pytest.mark.parametrize("sched", [False, True], ids=["index", "schedule"])
 @pytest.mark.parametrize("Cin", [2, 3, 8])
 def test_unpacked_gather(Cin, sched):
     c = Gather(Cin)
-    pos, kw = c.args(sched)
-    _lib().gather_batch(*pos, **kw)
+    d = c.args(sched)
+    assert d["nrows"] == (2 if sched else 0) and "noise" not in d
+    _lib().gather_batch(_stream(), d)
     torch.cuda.synchronize()
     got = c.out[:c.n_out].view(c.B, H, W, 8).cpu()
     want = bf16_rne(layout(c.X[list(ROWS)].double(), 0, 0)).float().bfloat16()
@@ -83,27 +83,32 @@ def test_unpacked_gather(Cin, sched):
     assert (z[4:36] == 0).all() and (z[:4] == 7).all() and (z[36:] == 7).all()  # only the zero range is cleared
     if sched:
         assert c.cursor.item() == 3                       # the gather reads the cursor, the optimizer advances it
+    # the functional layer builds the same launch
+    from mtl_das_pytorch_amd.ops import functional as F
+    o2, l2 = F.gather_batch(c.dX, c.dlab, c.idx, cursor=c.cursor)
+    assert torch.equal(_bits(o2.cpu()), _bits(got)) and torch.equal(l2.cpu(), c.lab[list(ROWS)])
 
 
 def test_gather_refusals():
-    """Each of these is refused by host code before any launch: csrc/misc.hip launch_gather_batch (rc = -2: Cin > 8,
-    taps with Cin != 1) and the binding (zero ranges, a cursor without its row count)."""
+    """Each of these is refused by host code before any launch: csrc/stem_gather.h gather_args_ok (rc = -2: Cin > 8,
+    taps with Cin != 1, a null output, an empty batch) and the binding (zero ranges, a cursor without its row
+    count)."""
     c = Gather(2)
-    pos, kw = c.args(True)
+    d = c.args(True)
     z = c.zero.data_ptr()
     bad = [
-        (dict(Cin=9), {}, "rc=-2"),
-        (dict(Cin=2), {"taps": 3, "off": 1}, "rc=-2"),
-        ({}, {"zero": [(z + 4, 32 * 4)]}, "zero range not 16-byte aligned"),
-        ({}, {"zero": [(z, 30)]}, "zero range not 16-byte aligned"),
-        ({}, {"zero": [(z, 16)] * 5}, "at most 4 zero ranges"),
-        ({}, {"nrows": 0}, "row count"),
+        ({"Cin": 9}, "rc=-2"),
+        ({"Cin": 2, "taps": 3, "off": 1}, "rc=-2"),
+        ({"zero": [(z + 4, 32 * 4)]}, "zero range not 16-byte aligned"),
+        ({"zero": [(z, 30)]}, "zero range not 16-byte aligned"),
+        ({"zero": [(z, 16)] * 5}, "at most 4 zero ranges"),
+        ({"nrows": 0}, "row count"),
+        ({"out": 0}, "rc=-2"),
+        ({"lab_out": 0}, "rc=-2"),
+        ({"B": 0}, "rc=-2"),
     ]
-    for p, k, msg in bad:
-        a = list(pos)
-        if "Cin" in p:
-            a[7] = p["Cin"]
+    for k, msg in bad:
         with pytest.raises(RuntimeError, match=msg):
-            _lib().gather_batch(*a, **{**kw, **k})
+            _lib().gather_batch(_stream(), {**d, **k})
     torch.cuda.synchronize()
     assert (c.out.float() == SENT).all() and (c.zero == 7).all() and (c.lab_out == int(SENT)).all()

@@ -140,7 +140,8 @@ def test_noise_off_is_the_step_that_never_heard_of_noise(data):
                 getattr(prog.flat, name).copy_(getattr(prog2.flat, name))
             r.pack_weights()
         ph = prog.gather_phase(data[0], data[1], r.idx, clear=True)
-        assert [(l.name, l.fn) for l in ph.launches if l.name != "clear"] == [("gather", k_gather)]
+        gathers = [l for l in ph.launches if l.name != "clear"]
+        assert [(l.name, l.fn) for l in gathers] == [("gather", k_gather)] and "noise" not in gathers[0].d
         for k in range(3):
             r.train_step(SCHED[k].cuda())
         torch.cuda.synchronize()

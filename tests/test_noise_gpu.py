@@ -155,7 +155,7 @@ def test_noise_gather_model_shape():
 def test_zero_power_equals_clean_gather(form):
     """Constant planes (a different constant per plane, one of them -0.0): sigma = 0 and the output is bitwise the
     clean gather's."""
-    from mtl_das_pytorch_amd.ops.hip import lib, ptr, stream
+    from mtl_das_pytorch_amd.ops import functional as F
     kind, a, b = form
     Cin, taps, off = (1, a, b) if kind == "pack" else (a, 0, 0)
     H, W, N = 9, 13, 5
@@ -163,11 +163,8 @@ def test_zero_power_equals_clean_gather(form):
     X[0] = -0.0
     c = Case(H, W, Cin, taps, off, False, X=X, rows=(4, 0, 4), snr=(-5.0, -5.0))
     assert (c.P[[4, 0]] == 0).all()
-    ref = torch.empty(3, H, W, 8, device="cuda", dtype=torch.bfloat16)
     lab = torch.zeros(N, 2, dtype=torch.int64, device="cuda")
-    lib().gather_batch(ptr(X.cuda()), ptr(torch.tensor([4, 0, 4]).cuda()), ptr(lab), 2, ptr(ref),
-                       ptr(torch.empty(3, 2, dtype=torch.int64, device="cuda")), 3, Cin, H, W, stream(), taps=taps,
-                       off=off)
+    ref, _ = F.gather_batch(X.cuda(), lab, torch.tensor([4, 0, 4]).cuda(), taps=taps, off=off)
     torch.cuda.synchronize()
     assert torch.equal(_bits(c.o), _bits(ref.cpu()))
     assert torch.equal(c.y, X[[4, 0, 4]]) and torch.equal(c.y.view(torch.int32), X[[4, 0, 4]].view(torch.int32))
@@ -218,12 +215,17 @@ def test_per_sample_snr_draw(form):
 def test_launcher_refuses_what_it_cannot_serve():
     from mtl_das_pytorch_amd.ops.hip import lib, stream
     c = Case(7, 10, 1, 3, 1, False)
-    d = {"X": c.Xc.cuda().data_ptr(), "idx": torch.tensor(c.rows).cuda().data_ptr(),
-         "lab": torch.zeros(5, 2, dtype=torch.int64, device="cuda").data_ptr(), "lab_w": 2, "out": c.out.data_ptr(),
-         "lab_out": torch.zeros(3, 2, dtype=torch.int64, device="cuda").data_ptr(), "B": 3, "Cin": 1, "H": 7, "W": 10,
-         "taps": 3, "off": 1, "power": c.P.data_ptr(), "snr": c.snr.data_ptr(), "draw": c.draw.data_ptr(),
-         "seed_lo": 1, "seed_hi": 2, "noise_stream": 0}
-    for bad in ({"power": 0}, {"Cin": 9, "taps": 0}, {"taps": 9}, {"Cin": 2}, {"snr": 0}, {"draw": 0}):
+    X, idx = c.Xc.cuda(), torch.tensor(c.rows).cuda()
+    lab = torch.zeros(5, 2, dtype=torch.int64, device="cuda")
+    lab_out = torch.zeros(3, 2, dtype=torch.int64, device="cuda")
+    nz = {"power": c.P.data_ptr(), "snr": c.snr.data_ptr(), "draw": c.draw.data_ptr(), "seed_lo": 1, "seed_hi": 2,
+          "noise_stream": 0}
+    d = {"X": X.data_ptr(), "idx": idx.data_ptr(), "lab": lab.data_ptr(), "lab_w": 2, "out": c.out.data_ptr(),
+         "lab_out": lab_out.data_ptr(), "B": 3, "Cin": 1, "H": 7, "W": 10, "taps": 3, "off": 1, "noise": nz}
+    c.out.fill_(SENT)
+    for bad in ({"noise": {**nz, "power": 0}}, {"Cin": 9, "taps": 0}, {"taps": 9}, {"Cin": 2},
+                {"noise": {**nz, "snr": 0}}, {"noise": {**nz, "draw": 0}}):
         with pytest.raises(RuntimeError, match="rc=-2"):
-            lib().gather_batch_noise(stream(), {**d, **bad})
+            lib().gather_batch(stream(), {**d, **bad})
     torch.cuda.synchronize()
+    assert (c.out.float() == SENT).all()  # a refused noisy launch has not run the clean kernel either

@@ -545,8 +545,12 @@ class Stem:
         out = self.bufs.fill((B_STEM, H, W, 8), torch.bfloat16, R.SENT, "packed batch")
         lab = self.bufs.fill((B_STEM, 2), torch.int64, -7, "gathered labels")
         cur = self.bufs.put(torch.tensor([cursor_value], dtype=torch.int64), "cursor")
-        _lib().gather_batch(P(self.dX), P(self.didx), P(self.dlab), 2, P(out), P(lab), B_STEM, 1, H, W, _stream(),
-                            taps=self.geom["taps"], off=self.geom["off"], zero=list(zero), cursor=P(cur), nrows=NROWS)
+        from mtl_das_pytorch_amd.ops.functional import gather_args
+        # (the launch dict on this case's guarded buffers: functional.gather_batch allocates its own labels)
+        d = gather_args(X=self.dX, labels=self.dlab, lab_w=2, idx=self.didx, out=out, lab_out=lab, B=B_STEM, H=H, W=W,
+                        taps=self.geom["taps"], off=self.geom["off"], zero=list(zero), cursor=cur)
+        assert d["nrows"] == NROWS and d["Cin"] == 1
+        _lib().gather_batch(_stream(), d)
         return out, lab, self.idx[cursor_value % NROWS]
 
 

@@ -1,12 +1,13 @@
 """Bitwise digest of a few captured training steps, for comparing two builds of the HIP extension.
 
-    python tools/ext_digest.py [--model MTL|multi_classifier|...] [--steps 5]
+    python tools/ext_digest.py [--model MTL|multi_classifier|...] [--steps 5] [--snr lo,hi [--noise-seed N]]
     MDA_EXT_PATH=ab/_mda_hip_base.so python tools/ext_digest.py ...
 
 Builds the model's program from the shipped tuned table (no measuring, so both builds run the same kernel
 configurations), trains ``--steps`` graph-replayed steps on a fixed synthetic batch schedule and prints the
 sha256 of the fp32 master weights, gradients, Adam moments and BN running statistics, and of the head's
-correct / count metric columns.
+correct / count metric columns, with the number of arrays and bytes hashed.  ``--snr lo,hi``: the steps train on
+noisy inputs (StepRunner.set_train_noise), so the digest also covers the noisy gather.
 Kernel changes that only reorder loads (no arithmetic change) must print the same digest as the baseline build.
 """
 import argparse
@@ -22,6 +23,8 @@ def main():
     ap.add_argument("--model", default="MTL")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--snr", type=str, default=None, metavar="LO,HI", help="train with on-device SNR noise (dB)")
+    ap.add_argument("--noise-seed", type=int, default=1)
     args = ap.parse_args()
     from mtl_das_pytorch_amd import use_engine_graph_queues
     use_engine_graph_queues()
@@ -51,20 +54,28 @@ def main():
     g = torch.Generator().manual_seed(7)
     sched = torch.stack([torch.randperm(n, generator=g)[:args.batch] for _ in range(args.steps)]).to(dev)
     runner.set_index_schedule(sched)
+    if args.snr is not None:
+        from mtl_das_pytorch_amd.data.noise import parse_snr_range
+        runner.set_train_noise(parse_snr_range(args.snr), seed=args.noise_seed)
     for _ in range(args.steps):
         runner.train_step()
     torch.cuda.synchronize()
     f = prog.flat
     h = hashlib.sha256()
+    arrays = nbytes = 0
     for name in ("params", "grads", "exp_avg", "exp_avg_sq", "bn_mean", "bn_var"):
         t = getattr(f, name, None)
         if t is not None:
-            h.update(t.detach().cpu().numpy().tobytes())
+            raw = t.detach().cpu().numpy().tobytes()
+            h.update(raw)
+            arrays, nbytes = arrays + 1, nbytes + len(raw)
     # the metric rows' correct / count columns (the loss column is an fp32 atomic sum: its last bits follow the
     # order the blocks arrive in, run to run)
-    hm = hashlib.sha256(prog.metrics[:, 1:3].detach().cpu().numpy().tobytes())
+    raw = prog.metrics[:, 1:3].detach().cpu().numpy().tobytes()
+    hm = hashlib.sha256(raw)
     print(f"DIGEST {args.model} steps={args.steps} state={h.hexdigest()[:16]} metrics={hm.hexdigest()[:16]} "
-          f"ext={os.environ.get('MDA_EXT_PATH', 'in-tree')}", flush=True)
+          f"ext={os.environ.get('MDA_EXT_PATH', 'in-tree')} snr={args.snr} arrays={arrays + 1} "
+          f"bytes={nbytes + len(raw)}", flush=True)
     runner.close()
 
 
