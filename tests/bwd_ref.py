@@ -14,10 +14,11 @@ import torch.nn.functional as F
 ACT_NONE, ACT_RELU, ACT_SIGMOID, SIGMUL, ADD_RELU, POOL_RELU = range(6)
 AMBIG = 1e-4   # |ReLU argument| (or gap between a pool window's two largest values) below which a mask may flip
 EPS = 1e-5
+DEVICE = "cpu"  # where the references compute (tests/layer_ref.py ``on`` moves whole layers to the GPU)
 
 
 def f64(t):
-    return t.detach().to("cpu", torch.float64)
+    return t.detach().to(DEVICE, torch.float64)
 
 
 def join(w, dy, in_hw, stride=1, padding=0, sources=()):
@@ -74,7 +75,7 @@ def mask(kind, y, consts, r=None, consts2=None, ambig=AMBIG):
     if kind == POOL_RELU:  # the gradient goes to the first maximum (row-major) of each window, if positive
         B, H, W, C = t.shape
         Hp, Wp = (H + 1) // 2, (W + 1) // 2
-        tp = torch.full((B, 2 * Hp, 2 * Wp, C), float("-inf"), dtype=torch.float64)
+        tp = torch.full((B, 2 * Hp, 2 * Wp, C), float("-inf"), dtype=torch.float64, device=t.device)
         tp[:, :H, :W] = t
         win = tp.view(B, Hp, 2, Wp, 2, C).permute(0, 1, 3, 5, 2, 4).reshape(B, Hp, Wp, C, 4)
         top, am = win.max(-1), win.argmax(-1)

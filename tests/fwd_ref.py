@@ -142,7 +142,7 @@ def conv2d_nhwc(x, w, b, c: FCase, pad_value=None, skip=None):
     if pad_value is not None:
         xp = pad_value.double().expand_as(xp).clone()
         xp[:, c.ph:c.ph + c.H, c.pw:c.pw + c.W] = x
-    y = torch.zeros(c.B, c.Ho, c.Wo, c.Co, dtype=torch.float64)
+    y = torch.zeros(c.B, c.Ho, c.Wo, c.Co, dtype=torch.float64, device=x.device)
     for kh in range(c.KH):
         for kw in range(c.KW):
             win = xp[:, kh:kh + (c.Ho - 1) * c.sh + 1:c.sh, kw:kw + (c.Wo - 1) * c.sw + 1:c.sw]
@@ -210,7 +210,7 @@ def pool2x2_ceil(t):
     H, W, C = t.shape[-3:]
     lead = t.shape[:-3]
     Hp, Wp = (H + 1) // 2, (W + 1) // 2
-    tp = torch.full(lead + (2 * Hp, 2 * Wp, C), float("-inf"), dtype=t.dtype)
+    tp = torch.full(lead + (2 * Hp, 2 * Wp, C), float("-inf"), dtype=t.dtype, device=t.device)
     tp[..., :H, :W, :] = t
     return tp.view(lead + (Hp, 2, Wp, 2, C)).amax((-2, -4))
 
@@ -488,25 +488,32 @@ class Checker:
             ok &= self.true(what + f" replica rows >= {nrep} zero", bool((stats[:, nrep:] == 0).all()))
         return ok
 
-    def consts(self, what, got, ref, beta):
+    def consts(self, what, got, ref, beta, extra=None):
         """Published constants [..., 4, C] against bn_consts: mean 2^-24 |mean|, invstd 4 2^-24 relative, scale
-        5 2^-24 relative, shift 8 2^-24 (|beta| + |mean scale|)."""
+        5 2^-24 relative, shift 8 2^-24 (|beta| + |mean scale|).  ``extra`` [..., 4, C] (rows as the constants):
+        what totals that are not exact may add to each (tests/layer_ref.py stat_slack)."""
         u = 2.0 ** -24
         r = ref.to(got.device)
         sc, sh, mu, inv = r.unbind(-2)
-        ok = self.bounded("mean", what, got[..., 2, :], mu, u * mu.abs())
-        ok &= self.bounded("invstd", what, got[..., 3, :], inv, 4 * u * inv.abs())
-        ok &= self.bounded("scale", what, got[..., 0, :], sc, 5 * u * sc.abs())
-        ok &= self.bounded("shift", what, got[..., 1, :], sh, 8 * u * (beta.double().to(got.device).abs() + (mu * sc).abs()))
+        x = torch.zeros_like(r) if extra is None else extra.to(got.device)
+        ok = self.bounded("mean", what, got[..., 2, :], mu, u * mu.abs() + x[..., 2, :])
+        ok &= self.bounded("invstd", what, got[..., 3, :], inv, 4 * u * inv.abs() + x[..., 3, :])
+        ok &= self.bounded("scale", what, got[..., 0, :], sc, 5 * u * sc.abs() + x[..., 0, :])
+        ok &= self.bounded("shift", what, got[..., 1, :], sh,
+                           8 * u * (beta.double().to(got.device).abs() + (mu * sc).abs()) + x[..., 1, :])
         return ok
 
-    def running_stats(self, what, rm, rv, rm0, rv0, mean, var, count, momentum):
-        """Running statistics after one step: |err| <= 4 2^-24 (|(1 - m) old| + |m new|), m the fp32 momentum."""
+    def running_stats(self, what, rm, rv, rm0, rv0, mean, var, count, momentum, extra=(0.0, 0.0)):
+        """Running statistics after one step: |err| <= 4 2^-24 (|(1 - m) old| + |m new|), m the fp32 momentum;
+        ``extra`` = (mean, biased variance) slack of totals that are not exact."""
         m, u = f32(momentum), 2.0 ** -24
         unb = var * count / (count - 1) if count > 1 else var
         ref_m, ref_v = running(rm0, rv0, mean, var, count, m)
-        ok = self.bounded("run_mean", what, rm, ref_m, 4 * u * (((1 - m) * rm0.double()).abs() + (m * mean).abs()))
-        ok &= self.bounded("run_var", what, rv, ref_v, 4 * u * (((1 - m) * rv0.double()).abs() + (m * unb).abs()))
+        xv = extra[1] * count / (count - 1) if count > 1 else extra[1]
+        ok = self.bounded("run_mean", what, rm, ref_m,
+                          4 * u * (((1 - m) * rm0.double()).abs() + (m * mean).abs()) + m * extra[0])
+        ok &= self.bounded("run_var", what, rv, ref_v,
+                           4 * u * (((1 - m) * rv0.double()).abs() + (m * unb).abs()) + m * xv)
         return ok
 
     def act(self, what, got, ref, extra=None, kind="act"):

@@ -15,6 +15,9 @@ model/modelB_singleTask.py) for each task -- and over A's input channels: 1 (the
 stored input, the unpacked 7x7 stem at K = 392 padded to 416 and its weight gradient / finalize); plus A's
 data-parallel backward program (2 gradient buckets: the backward cut into pieces, weight gradients and
 finalize per piece), run here without collectives.
+
+The forward of the same fixture (``fwd_train``, and ``fwd_eval`` after the step) is checked layer by layer at the
+end of this module against the fp64 references and derived bounds of tests/layer_ref.py.
 """
 import pytest
 import torch
@@ -96,6 +99,7 @@ def engine_step(request):
     prog.flat.sync_module_grads()
     yield model, prog, X, labels
     torch.backends.cudnn.enabled, torch.backends.cudnn.allow_tf32, torch.backends.cuda.matmul.allow_tf32 = flags
+    torch.cuda.empty_cache()  # the forward tests' fp64 references of whole layers are not left to the later modules
 
 
 class Checker:
@@ -288,4 +292,167 @@ def test_mtl_backward_layer_local(engine_step):
         scale = prog.loss_weights[t] / (prog.B * gsz * A4.H * A4.W)
         ref = (p * scale).repeat_interleave(gsz, 1)[:, :, None, None].expand(-1, -1, A4.H, A4.W)
         chk("dhead", f"head task{t} dA4", nchw(prog.dA4, t), ref)
+    chk.done()
+
+
+# ---------------------------------------------------------------------------------------------------
+# The forward, layer by layer (tests/layer_ref.py: fp64 references on the device, derived bounds).  Inputs follow the
+# module's dataflow (model/modelA_MTL.py:127-174: conv1, the residual blocks, per task and level the generator on
+# cat[F, B_prev], the mask multiply, the encoder block and its ceil-mode pool), each built from the ENGINE's outputs
+# of the earlier ops, so one wrong layer fails alone.  The tests use the module-scoped fixture in file order: the
+# eval forward overwrites the activations the training forward stored, so it comes last.
+def nhwc(a, z=0, c0=0, C=None):
+    """Group z, channels [c0, c0 + C) of an engine NHWC activation as dense fp64 [B, H, W, C]."""
+    C = a.C - c0 if C is None else C
+    t = a.t.reshape(-1)[a.off + z * a.gs + c0:]
+    M = a.B * a.H * a.W
+    idx = torch.arange(M, device=t.device)[:, None] * a.ld + torch.arange(C, device=t.device)[None]
+    return t[idx].double().view(a.B, a.H, a.W, C)
+
+
+class Forward:
+    """One forward phase of the fixture's program against tests/layer_ref.py; ``training``: batch statistics, published
+    constants and running statistics (fresh modules before the step: mean 0, variance 1, no batch tracked), else the
+    eval constants of the running statistics the step left."""
+
+    def __init__(self, prog, training):
+        import layer_ref as L
+        self.L, self.prog, self.training, self.chk = L, prog, training, L.Checker()
+
+    def consts(self, bn, z):
+        """What the tails and normalise-on-load consumers of BN ``bn`` evaluate: the fp32 constants the training
+        forward published, or the fp64 eval constants (the eval forward publishes none)."""
+        m = bn.mods[z]
+        if self.training:
+            return bn.consts[z].double()
+        return self.L.bn_eval(m.running_mean, m.running_var, m.weight.detach(), m.bias.detach(), bn.eps)
+
+    def conv(self, name, conv, member, z, x, y, bn, nol=None):
+        """Conv ``member`` of ``conv`` (group z) on ``x`` -- or, normalise-on-load, on the operand rebuilt from
+        ``nol`` = (producer's stored y, its BN, z) -- against the stored pre-BN ``y`` and the BN that follows."""
+        L, chk = self.L, self.chk
+        m = conv.members[member][0] if conv.concat else conv.mods[z]
+        bias = None if m.bias is None else m.bias.detach()
+        if nol is None:
+            f = L.conv_fwd(x, m.weight.detach(), m.stride, m.padding, bias)
+            amb = None
+        else:
+            yp, bnp, zp = nol
+            k = self.consts(bnp, zp)
+            slack = 0.0 if self.training else L.eval_nol_slack(yp, k, bnp.mods[zp].bias.detach())
+            f = L.nol_conv_fwd(yp, k[0], k[1], L.ACT_RELU, m.weight.detach(), m.stride, m.padding, bias, slack)
+            chk.true(f"{name} operand ambiguity below 1 %", float(f["amb_map"].double().mean()) <= 0.01)
+            amb = f["amb"]
+        chk.acc("y" if nol is None else "nol y", f"{name} y", y, f["y"], f["abs"], f["n"], amb)
+        if self.training:
+            b = bn.mods[z]
+            ref = L.bn_train(f["y"], f["abs"], f["n"], b.weight.detach(), b.bias.detach(), bn.eps, amb)
+            run = (b.running_mean, b.running_var, torch.zeros_like(b.running_mean), torch.ones_like(b.running_var),
+                   b.num_batches_tracked, 0)
+            chk.bn_training(f"{name} BN", bn.consts[z], ref, b.bias.detach(), run, bn.momentum)
+
+    def tail(self, name, kind, y, bn, z, out, r=None, bn2=None):
+        k2 = None if bn2 is None else self.consts(bn2, z)
+        self.chk.ulp("tail", name, out, self.L.tail_fwd(kind, y, self.consts(bn, z), r, k2))
+
+
+def forward_layer_local(engine_step, training):
+    import layer_ref as L
+    model, prog, X, labels = engine_step
+    T, lv, rbs = prog.T, prog.levels, prog.rbs
+    fw = Forward(prog, training)
+    chk = fw.chk
+    with L.on("cuda"):
+        # ---- stem: conv of q(X) (1 channel: the packed taps; 2: unpacked over 8 stored channels)
+        xq = q(X).double().permute(0, 2, 3, 1).contiguous()
+        fw.conv("conv1.0", prog.conv1, 0, 0, xq, nhwc(prog.y0), prog.bn1)
+        fw.tail("conv1 tail", L.ACT_RELU, nhwc(prog.y0), prog.bn1, 0, nhwc(prog.f0))
+        # ---- residual blocks
+        for i, R in enumerate(rbs):
+            nm = f"resblock{i + 1}"
+            xin = nhwc(R["in"])
+            if R.get("fused"):   # [ya | ys]: each member's slice against its own conv
+                fw.conv(f"{nm}.left.0", R["cas"], 0, 0, xin, nhwc(R["ya"]), R["bna"])
+                fw.conv(f"{nm}.shortcut.0", R["cas"], 1, 0, xin, nhwc(R["ys"]), R["bns"])
+            else:
+                fw.conv(f"{nm}.left.0", R["ca"], 0, 0, xin, nhwc(R["ya"]), R["bna"])
+                if R["proj"]:
+                    fw.conv(f"{nm}.shortcut.0", R["cs"], 0, 0, xin, nhwc(R["ys"]), R["bns"])
+            if prog.nol_for(R["cb"]):
+                fw.conv(f"{nm}.left.3", R["cb"], 0, 0, None, nhwc(R["yb"]), R["bnb"], nol=(nhwc(R["ya"]), R["bna"], 0))
+            else:
+                fw.tail(f"{nm} inner tail", L.ACT_RELU, nhwc(R["ya"]), R["bna"], 0, nhwc(R["ha"]))
+                fw.conv(f"{nm}.left.3", R["cb"], 0, 0, nhwc(R["ha"]), nhwc(R["yb"]), R["bnb"])
+            if R["proj"]:
+                fw.tail(f"{nm} tail", L.ADD_RELU, nhwc(R["yb"]), R["bnb"], 0, nhwc(R["out"]), r=nhwc(R["ys"]), bn2=R["bns"])
+            else:
+                fw.tail(f"{nm} tail", L.ADD_RELU, nhwc(R["yb"]), R["bnb"], 0, nhwc(R["out"]), r=xin)
+        # ---- task levels
+        for li, Lv in enumerate(lv):
+            for t in range(T):
+                nm = f"level{li + 1}.task{t}"
+                x = nhwc(Lv["Fa"]) if Lv["prevB"] is None else torch.cat([nhwc(Lv["Fa"]), nhwc(Lv["prevB"], t)], -1)
+                fw.conv(f"{nm}.gen_conv0", Lv["c0"], 0, t, x, nhwc(Lv["ym1"], t), Lv["bn0"])
+                if prog.nol_for(Lv["c3"]):
+                    fw.conv(f"{nm}.gen_conv3", Lv["c3"], 0, t, None, nhwc(Lv["ym2"], t), Lv["bn3"],
+                            nol=(nhwc(Lv["ym1"], t), Lv["bn0"], t))
+                else:
+                    fw.tail(f"{nm} gen tail", L.ACT_RELU, nhwc(Lv["ym1"], t), Lv["bn0"], t, nhwc(Lv["hm"], t))
+                    fw.conv(f"{nm}.gen_conv3", Lv["c3"], 0, t, nhwc(Lv["hm"], t), nhwc(Lv["ym2"], t), Lv["bn3"])
+                fw.tail(f"{nm} mask tail", L.SIGMUL, nhwc(Lv["ym2"], t), Lv["bn3"], t, nhwc(Lv["Aout"], t), r=nhwc(Lv["Fb"]))
+                if "co" in Lv:
+                    fw.conv(f"{nm}.out_conv", Lv["co"], 0, t, nhwc(Lv["Aout"], t), nhwc(Lv["yo"], t), Lv["bno"])
+                    fw.tail(f"{nm} pool tail", L.POOL_RELU, nhwc(Lv["yo"], t), Lv["bno"], t, nhwc(Lv["Bp"], t))
+    return chk
+
+
+def head_check(chk, model, prog, labels, metrics, confusion):
+    """logp, metrics and the confusion matrix of ONE batch from the engine's A4, at test_heads_gpu's bounds: logp max
+    abs 1e-4, loss sum relative 1e-4, the counts and the confusion matrix exact (a prediction whose two largest fp64
+    logits are within 1e-5 is taken from the engine's own log-probabilities)."""
+    A4 = prog.levels[3]["Aout"]
+    for t in range(prog.T):
+        K = model.task_cate_num[t]
+        lab = labels[:, prog.lab_off[t]]
+        z = nhwc(A4, t).mean((1, 2)).view(prog.B, K, A4.C // K).mean(-1)
+        lp = torch.log_softmax(z, 1)
+        got = prog.logp[t, :, :K].double()
+        chk.bounded("logp abs err / 1e-4", f"task{t} logp", got, lp, torch.full_like(lp, 1e-4))
+        top = z.topk(2, 1).values
+        decided = (top[:, 0] - top[:, 1]) > 1e-5
+        pred = torch.where(decided, z.argmax(1), got.argmax(1))
+        chk.exact(f"task{t} decided predictions", got.argmax(1)[decided], z.argmax(1)[decided])
+        nll = -lp[torch.arange(prog.B), lab].sum()
+        chk.bounded("loss sum rel err / 1e-4", f"task{t} loss", metrics[t, 0], nll, 1e-4 * nll.abs())
+        chk.exact(f"task{t} correct, count, |pred - label|", metrics[t, 1:],
+                  torch.stack([(pred == lab).sum(), torch.tensor(prog.B, device=lab.device), (pred - lab).abs().sum()]))
+        cm = torch.zeros(16, 16, dtype=torch.int64, device=lab.device)
+        cm.index_put_((lab, pred), torch.ones_like(lab), accumulate=True)
+        chk.exact(f"task{t} confusion", confusion[t], cm)
+
+
+def test_mtl_forward_train_layer_local(engine_step):
+    """Every op of ``fwd_train`` at the benchmarked batch and tuned configs: the stored pre-BN y (one fp32 accumulation,
+    one rounding: 2^-8 |ref| + n 2^-24 conv(|x|, |w|), plus the operand ambiguity of a normalise-on-load conv), the
+    published BN constants and running statistics against the fp64 statistics of the unrounded reference y, every tail
+    output within one bf16 ulp of its fp64 value, the head's log-probabilities, metrics and confusion matrix."""
+    model, prog, X, labels = engine_step
+    chk = forward_layer_local(engine_step, True)
+    head_check(chk, model, prog, labels, prog.metrics.double(), prog.confusion.long())
+    chk.done()
+
+
+def test_mtl_forward_eval_layer_local(engine_step):
+    """``fwd_eval`` (its own ``st0`` configs) on the same batch after the step moved the running statistics: the same
+    checks with the eval constants, the metrics of this batch as the increment of the accumulated ones."""
+    model, prog, X, labels = engine_step
+    met0, cm0 = prog.metrics.double().clone(), prog.confusion.long().clone()
+    state = [b.clone() for b in (prog.flat.bn_mean, prog.flat.bn_var, prog.flat.bn_nbt)]
+    prog.fwd_eval.run()
+    torch.cuda.synchronize()
+    chk = forward_layer_local(engine_step, False)
+    now = (prog.flat.bn_mean, prog.flat.bn_var, prog.flat.bn_nbt)
+    for name, b, b0 in zip(("mean", "var", "num_batches_tracked"), now, state):
+        chk.bits(f"running {name} unchanged by the eval forward", b, b0)
+    head_check(chk, model, prog, labels, prog.metrics.double() - met0, prog.confusion.long() - cm0)
     chk.done()
