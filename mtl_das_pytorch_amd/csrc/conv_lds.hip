@@ -473,9 +473,11 @@ int make_plan(int mode, const ConvArgs& a, const LdsCfg& c, LdsPlan& pl, int& gx
     P.ay = -a.ph; P.ax = -a.pw;
   } else {
     pl.mh = 1; pl.mw = 1; pl.by = -1; pl.bx = -1; pl.th = a.sh; pl.tw = a.sw; pl.qy = a.sh; pl.qx = a.sw;
+    const int nphy = std::min(a.sh, a.Ho), nphx = std::min(a.sw, a.Wo);
+    if (nphy < 1 || nphx < 1 || nphy * nphx > 4) return -2;  // pl.ph holds 4 phases (stride 3 would write 9)
     int n = 0;
-    for (int py = 0; py < std::min(a.sh, a.Ho); ++py)
-      for (int px = 0; px < std::min(a.sw, a.Wo); ++px) {
+    for (int py = 0; py < nphy; ++py)
+      for (int px = 0; px < nphx; ++px) {
         LdsPhase& P = pl.ph[n++];
         P.oy0 = py; P.ox0 = px;
         P.Hq = (a.Ho - py + a.sh - 1) / a.sh;
@@ -488,7 +490,6 @@ int make_plan(int mode, const ConvArgs& a, const LdsCfg& c, LdsPlan& pl, int& gx
         P.ax = (px + a.pw - P.rw) / a.sw;
       }
     pl.nph = n;
-    if (n < 1 || n > 4) return -2;
   }
   gx = 0;
   for (int p = 0; p < pl.nph; ++p) {

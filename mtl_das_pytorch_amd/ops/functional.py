@@ -237,8 +237,11 @@ def _rows(t: torch.Tensor, lead: int, what: str) -> Tuple[int, int]:
 
 
 def prepare_conv2d_dgrad(dy, w, in_hw, stride=1, padding=0, cin_stored=None, cfg=None, bn_stats=None, groups=None,
-                         add=None) -> ConvCall:
-    """``bn_stats`` (optional): ``(y, bn, part, kind)`` -- the dgrad output is the gradient of
+                         add=None, out=None) -> ConvCall:
+    """``dy`` may be the column slice of a wider buffer (a branch conv's share of a concat gradient).  ``out``: the
+    bf16 ``[(G,) B, H, W, Cin_stored]`` gradient to write instead of a new one, possibly the column slice of a wider
+    buffer (the groups of ``dy`` / ``out`` one stride apart).
+    ``bn_stats`` (optional): ``(y, bn, part, kind)`` -- the dgrad output is the gradient of
     ``act(BN(y))`` and the epilogue accumulates that BN's backward sums sum(dz), sum(dz*xhat) into rows 0/1
     of ``part`` ([NREP, 3, C] fp64, zero-initialised); see :func:`bn_tail_backward` ``stats_done``.  Or a dict
     with those four keys and optionally ``r`` (ADD_RELU: the residual), ``bn2`` (its BN: projection shortcut, row
@@ -251,9 +254,13 @@ def prepare_conv2d_dgrad(dy, w, in_hw, stride=1, padding=0, cin_stored=None, cfg
     ``part`` is ``[G, NREP, 3, C]`` and the BN parameters ``[G, C]`` (:func:`bn_args`)."""
     G = groups or 1
     lead = 1 if groups else 0
-    _check(dy, torch.bfloat16)
+    if not dy.is_cuda:
+        raise RuntimeError("HIP ops need a GPU tensor")
+    if dy.dtype != torch.bfloat16:
+        raise TypeError(f"expected {torch.bfloat16}, got {dy.dtype}")
     if dy.dim() != 4 + lead or w.dim() != 4 + lead or (lead and (dy.shape[0] != G or w.shape[0] != G)):
         raise ValueError("dgrad: dy [(G,) B, Ho, Wo, Co] and w [(G,) Co, Ci, KH, KW] expected")
+    ld0, gs0 = _rows(dy, lead, "dy")
     B, Ho, Wo, Co = dy.shape[lead:]
     _, Ci, KH, KW = w.shape[lead:]
     Cs = cin_stored or Ci
@@ -265,10 +272,16 @@ def prepare_conv2d_dgrad(dy, w, in_hw, stride=1, padding=0, cin_stored=None, cfg
     else:
         wd = pack_weight_dgrad(w.float(), Cs)
     from ..engine import guard
-    dx = guard.alloc(((G,) if lead else ()) + (B, H, W, Cs), torch.bfloat16, dy.device, label=f"dgrad out cfg {cfg}")
-    d = {"src": {"p0": ptr(dy), "ld0": Co, "C0": Co, "C1": 0, "gs0": B * Ho * Wo * Co if lead else 0},
-         "w": ptr(wd), "wgs": wd.shape[-2] * wd.shape[-1] if lead else 0, "out": ptr(dx), "ldo": Cs,
-         "ogs": B * H * W * Cs if lead else 0,
+    oshape = ((G,) if lead else ()) + (B, H, W, Cs)
+    if out is None:
+        dx = guard.alloc(oshape, torch.bfloat16, dy.device, label=f"dgrad out cfg {cfg}")
+    else:
+        dx = out
+        if tuple(dx.shape) != oshape:
+            raise ValueError(f"out must be {oshape}")
+    ldo, ogs = _rows(dx, lead, "out")
+    d = {"src": {"p0": ptr(dy), "ld0": ld0, "C0": Co, "C1": 0, "gs0": gs0},
+         "w": ptr(wd), "wgs": wd.shape[-2] * wd.shape[-1] if lead else 0, "out": ptr(dx), "ldo": ldo, "ogs": ogs,
          "B": B, "Hs": Ho, "Ws": Wo, "Ho": H, "Wo": W, "N": Cs, "Npad": wd.shape[-2], "Cs": Co, "KH": KH, "KW": KW,
          "sh": sh, "sw": sw, "ph": ph, "pw": pw, "Kpad": wd.shape[-1]}
     keep = (dy, wd)
@@ -308,9 +321,10 @@ def prepare_conv2d_dgrad(dy, w, in_hw, stride=1, padding=0, cin_stored=None, cfg
 
 
 def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, in_hw: Tuple[int, int], stride=1, padding=0,
-                 cin_stored: Optional[int] = None, cfg: Optional[int] = None, bn_stats=None, groups=None, add=None):
+                 cin_stored: Optional[int] = None, cfg: Optional[int] = None, bn_stats=None, groups=None, add=None,
+                 out: Optional[torch.Tensor] = None):
     """Gradient w.r.t. the NHWC input: bf16 ``[B, H, W, Cin_stored]`` (fp32 accumulation, one rounding)."""
-    return prepare_conv2d_dgrad(dy, w, in_hw, stride, padding, cin_stored, cfg, bn_stats, groups, add).run()
+    return prepare_conv2d_dgrad(dy, w, in_hw, stride, padding, cin_stored, cfg, bn_stats, groups, add, out).run()
 
 
 WGRAD_TILES = {0: (16, 32, 128), 1: (32, 32, 128), 2: (32, 64, 64), 3: (64, 64, 64), 4: (16, 64, 128),

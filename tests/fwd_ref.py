@@ -89,7 +89,10 @@ def in_view(buf, c: FCase, seg=0):
     return buf[:, :P * ld].view(c.G, c.B, c.H, c.W, ld)[..., off:off + C]
 
 
-def _in_buf(vals, c, seg):
+def in_buf(vals, c, seg=0):
+    """``vals`` [G, B, H, W, C] as segment ``seg``'s flat bf16 buffer, NaN outside the addressed slice.  Like the
+    views above and the output builders below it takes any record with the fields it names (tests/dgrad_ref.py
+    addresses a dgrad's dy and dx through them)."""
     ld = c.ld1 if seg else c.ld0
     P = c.B * c.H * c.W
     buf = torch.full((c.G, P * ld + c.gap), NAN)
@@ -129,7 +132,7 @@ def conv_inputs(c: FCase) -> dict:
         x = ints(g, (c.G, c.B, c.H, c.W, c.Cs), 4)
         w = ints(g, (c.G, c.Co, c.Cs, c.KH, c.KW), c.wlim, 0.375 if c.wlim > 1 else 0.25)
         b = ints(g, (c.G, c.Co), 8, 0.0)
-    return {"buf0": _in_buf(x[..., :c.C0], c, 0), "buf1": _in_buf(x[..., c.C0:], c, 1) if c.C1 else None,
+    return {"buf0": in_buf(x[..., :c.C0], c, 0), "buf1": in_buf(x[..., c.C0:], c, 1) if c.C1 else None,
             "w": w, "b": b if c.bias else None, "x": x.double()}
 
 
@@ -333,7 +336,7 @@ def nol_inputs(c: FCase, big_shift=False) -> dict:
     ``w`` [G, Co, Cs, KH, KW].  ``big_shift``: |beta| ~ 3, so that BN(0) = shift in the padding would be far off."""
     g = gen(9000 + c.seed)
     y = (2 * torch.randn(c.G, c.B, c.H, c.W, c.Cs, generator=g) + 0.3).bfloat16()
-    d = {"y": y, "buf0": _in_buf(y.float(), c, 0),
+    d = {"y": y, "buf0": in_buf(y.float(), c, 0),
          "gamma": torch.rand(c.G, c.Cs, generator=g) + 0.5, "beta": 0.1 * torch.randn(c.G, c.Cs, generator=g),
          "rm": 0.5 * torch.randn(c.G, c.Cs, generator=g), "rv": 0.5 + torch.rand(c.G, c.Cs, generator=g),
          "w": (torch.randn(c.G, c.Co, c.Cs, c.KH, c.KW, generator=g) / c.K ** 0.5).bfloat16().float()}
