@@ -8,6 +8,8 @@
     python infer.py ... --gate_db 3 [--noise_floor auto|P]   # evaluate only windows 3 dB above the noise floor
     python infer.py ... --chunk 2000 --gate_db 3 --noise_floor running [--floor_history 64]   # the gate on the chunked
         # run: the floor is the running median of the last 64 time indices (or --noise_floor P, a fixed power)
+    python infer.py ... --decimate 10 [--taps taps.npy] [--chunk 20000]   # the recording is at the raw rate (fp32 or
+        # int16): low-pass FIR and decimation by 10 first; --chunk then counts raw samples
 """
 import argparse
 import os
@@ -45,7 +47,25 @@ def main():
     ap.add_argument("--floor_warmup", type=int, default=None,
                     help="with --noise_floor running: every window is active until this many time indices exist "
                          "(default: 8, at most --floor_history)")
+    ap.add_argument("--decimate", type=int, default=None,
+                    help="the recording is at the raw rate (float or int16): anti-alias FIR and decimation by this "
+                         "factor (1 .. 64) ahead of the windows; --chunk then counts raw samples")
+    ap.add_argument("--taps", default=None,
+                    help="with --decimate: the FIR's taps, a .npy vector of at most 1025 (default: a Kaiser-windowed "
+                         "sinc of 16 * D + 1 taps with its cut-off at 0.375 / D)")
     args = ap.parse_args()
+    taps = None
+    if args.taps is not None and args.decimate is None:
+        ap.error("--taps needs --decimate")
+    if args.decimate is not None:
+        import numpy
+        from mtl_das_pytorch_amd.data.resample import as_taps
+        try:
+            if args.taps is not None:
+                taps = numpy.load(args.taps, allow_pickle=False)
+            taps = as_taps(taps, args.decimate)
+        except (ValueError, OSError) as e:
+            ap.error(f"--decimate / --taps: {e}")
     noise_floor = args.noise_floor
     if args.gate_db is not None and args.chunk is not None and noise_floor == "auto":
         ap.error("--gate_db with --chunk needs --noise_floor running (or a power): 'auto' is the median over the "
@@ -93,24 +113,36 @@ def main():
             rec = np.asarray(load_mat(args.recording, (args.key,)), dtype=np.float32)
         else:
             rec = np.load(args.recording, mmap_mode="r", allow_pickle=False)
-        res, live_maps = live_run(model, args, rec, stride, cell if args.map else None, ctx, use_engine, noise_floor)
+        if rec.dtype == np.int16 and args.decimate is None:
+            ap.error("an int16 recording is at the raw rate: it needs --decimate")
+        res, live_maps = live_run(model, args, rec, stride, cell if args.map else None, ctx, use_engine, noise_floor,
+                                  taps)
     else:
         if args.recording.endswith(".mat"):
             rec = np.asarray(load_mat(args.recording, (args.key,)), dtype=np.float32)
         else:
-            rec = np.load(args.recording, allow_pickle=False).astype(np.float32)
+            rec = np.load(args.recording, allow_pickle=False)
+            if rec.dtype == np.int16 and args.decimate is None:
+                ap.error("an int16 recording is at the raw rate: it needs --decimate")
+            if rec.dtype != np.int16:  # int16 is uploaded as it is
+                rec = rec.astype(np.float32)
         res = predict_recording(model, args.model, torch.from_numpy(rec), stride=stride, batch=args.batch_size,
-                                ctx=ctx, use_engine=use_engine, gate_db=args.gate_db, noise_floor=noise_floor)
+                                ctx=ctx, use_engine=use_engine, gate_db=args.gate_db, noise_floor=noise_floor,
+                                decimate=args.decimate, taps=taps)
     if ctx.is_main:
         import pandas as pd
         cols = {"fiber_start": res["positions"][:, 0], "time_start": res["positions"][:, 1]}
-        for k in ("distance_pred", "event_pred", "joint_pred", "power_db", "active"):
+        for k in ("raw_time_start", "raw_time_stop", "distance_pred", "event_pred", "joint_pred", "power_db", "active"):
             if k in res:
                 cols[k] = res[k].astype(np.int64) if k == "active" else res[k]
         pd.DataFrame(cols).to_csv(args.out, index=False)
         print(f"{len(res['positions'])} windows -> {args.out}")
         if args.map:
             shape = rec.shape[-2:]
+            extra = {}
+            if args.decimate is not None:  # the maps are the decimated recording's
+                from mtl_das_pytorch_amd.data.resample import output_count
+                shape = (shape[0], output_count(shape[1], len(taps), args.decimate))
             if live_maps is not None:
                 maps = live_maps
             else:
@@ -122,33 +154,41 @@ def main():
                     probs = torch.from_numpy(probs).to(ctx.device)
                 maps = prediction_map(probs, fs, ts, shape, cell, active=res.get("active"))
             nfc, ntc = next(iter(maps.values())).shape[-2:]
+            if args.decimate is not None:
+                extra = {"time_edges_raw": np.minimum(np.arange(ntc + 1) * cell[1], shape[1]) * args.decimate,
+                         "decimate": args.decimate, "taps": taps}
             np.savez(args.map, fiber_edges=np.minimum(np.arange(nfc + 1) * cell[0], shape[0]),
-                     time_edges=np.minimum(np.arange(ntc + 1) * cell[1], shape[1]), **maps)
+                     time_edges=np.minimum(np.arange(ntc + 1) * cell[1], shape[1]), **extra, **maps)
             print(f"{nfc} x {ntc} cells -> {args.map}")
     shutdown(ctx)
 
 
-def live_run(model, args, rec, stride, cell, ctx, use_engine, noise_floor="running"):
+def live_run(model, args, rec, stride, cell, ctx, use_engine, noise_floor="running", taps=None):
     """The recording through a LiveRecording, ``--chunk`` time samples at a time: the result dict of
     predict_recording (windows in its order) and, with ``cell``, the maps of prediction_map.  With ``--gate_db`` the
-    live gate at ``noise_floor`` ("running" or a power)."""
+    live gate at ``noise_floor`` ("running" or a power).  With ``--decimate`` the chunks are raw (an int16 recording
+    is pushed as int16) and the ring counts decimated samples."""
     import numpy as np
     from mtl_das_pytorch_amd.inference import WINDOW, LiveRecording
     rec3 = rec if rec.ndim == 3 else rec[None]
     C, F, T = rec3.shape
-    ring = args.ring if args.ring is not None else max(8 * WINDOW[1], WINDOW[1] + min(args.chunk, 1 << 14))
+    D = args.decimate or 1
+    ring = args.ring if args.ring is not None else max(8 * WINDOW[1], WINDOW[1] + min(-(-args.chunk // D), 1 << 14))
     live = LiveRecording(model, args.model, F, C=C, stride=stride, cell=cell, ring=ring, batch=args.batch_size,
                          ctx=ctx, use_engine=use_engine, gate_db=args.gate_db,
                          noise_floor=noise_floor if args.gate_db is not None else "running",
-                         floor_history=args.floor_history, floor_warmup=args.floor_warmup or 1)
+                         floor_history=args.floor_history, floor_warmup=args.floor_warmup or 1,
+                         decimate=args.decimate, taps=taps)
+    dtype = np.int16 if (args.decimate is not None and rec3.dtype == np.int16) else np.float32
     outs = []
     for t in range(0, T, args.chunk):
-        outs.append(live.push(np.ascontiguousarray(rec3[:, :, t:t + args.chunk], dtype=np.float32)))
+        outs.append(live.push(np.ascontiguousarray(rec3[:, :, t:t + args.chunk], dtype=dtype)))
     outs.append(live.flush())
     live.close()
     pos = np.concatenate([o["positions"] for o in outs])
     if len(pos) == 0:
-        raise ValueError(f"recording dimension {T} is shorter than the window {WINDOW[1]}")
+        raise ValueError(f"recording dimension {T} is shorter than the window {WINDOW[1]}"
+                         + (f" times the decimation {D}" if args.decimate is not None else ""))
     order = np.lexsort((pos[:, 1], pos[:, 0]))  # fiber-major, as the whole-recording table
     res = {k: np.concatenate([o[k] for o in outs])[order] for k in outs[0] if k != "map_columns"}
     maps = None

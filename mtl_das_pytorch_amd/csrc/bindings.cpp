@@ -519,6 +519,18 @@ void live_select(int64_t stream, py::dict d) {
                            (int)I(d, "pitch"), P<int64_t>(d, "offs"), I(d, "noffs"), S(stream)), "live_select");
 }
 
+// a refused fir_decimate is the caller's argument error: ValueError
+void fir_decimate(int64_t stream, py::dict d) {
+  FirArgs a{};
+  a.raw = P<const void>(d, "raw"); a.carry_in = P<const float>(d, "carry_in"); a.taps = P<const float>(d, "taps");
+  a.out = P<float>(d, "out"); a.carry_out = P<float>(d, "carry_out");
+  a.rows = I(d, "rows"); a.n = I(d, "n"); a.pitch = I(d, "pitch"); a.m = I(d, "m");
+  a.carry_len = (int)I(d, "carry_len"); a.skip = (int)I(d, "skip"); a.D = (int)I(d, "D"); a.L = (int)I(d, "L");
+  const int rc = launch_fir_decimate(a, (int)I(d, "itype"), S(stream));
+  if (rc == -2) throw py::value_error("fir_decimate: arguments refused (rc=-2)");
+  check(rc, "fir_decimate");
+}
+
 void pool3(int is_max, int backward, int64_t stream, py::dict d) {
   PoolArgs a{};
   a.x = P<const bf16_t>(d, "x"); a.ldx = (int)I(d, "ldx");
@@ -657,6 +669,11 @@ PYBIND11_MODULE(_mda_hip, m) {
   m.def("running_floor", &running_floor);
   m.def("live_select", &live_select);
   m.def("live_map", &live_map,py::arg("stream"), py::arg("d"), py::arg("fs"), py::arg("jlo"), py::arg("jn"));
+  m.def("fir_decimate", &fir_decimate);
+  m.def("fir_output_count", &fir_output_count);
+  m.attr("DECIMATE_TILE") = DECIMATE_TILE;
+  m.attr("DECIMATE_MAX_FACTOR") = DECIMATE_MAX_FACTOR;
+  m.attr("DECIMATE_MAX_TAPS") = DECIMATE_MAX_TAPS;
   m.def("wgrad_table", &wgrad_table);
   m.def("wgrad_batched", &wgrad_batched, py::arg("cfg"), py::arg("table"), py::arg("nj"), py::arg("nblocks"),
         py::arg("stream"), py::arg("cap") = 0);

@@ -482,6 +482,29 @@ int launch_running_floor(const LiveGateArgs& a, int history, int warmup, hipStre
 // select_blocks(n1 - n0) entries
 int launch_live_select(const LiveGateArgs& a, float ratio, float* table, int64_t nrows, int pitch, int64_t* offs,
                        int64_t noffs, hipStream_t st);
+// resample.hip: raw-rate recordings -- a FIR and decimation by D along time, one piece of a stream per launch
+// (data/resample.py is the definition).  The piece's samples are carry_in's live columns followed by raw[skip ..];
+// out gets the m outputs they complete, in ring_append's chunk layout, carry_out the new tail.
+constexpr int DECIMATE_TILE = 128;        // outputs of one block
+constexpr int DECIMATE_THREADS = 64;
+constexpr int DECIMATE_MAX_FACTOR = 64;   // 1 <= D
+constexpr int DECIMATE_MAX_TAPS = 1025;   // 1 <= L
+enum { FIR_F32 = 0, FIR_I16 = 1 };        // the type of raw
+struct FirArgs {
+  const void* raw;        // [rows][pitch], n live columns: fp32 or int16
+  const float* carry_in;  // [rows][L - 1], carry_len live columns: the raw samples from the next output's support on
+  const float* taps;      // [L]
+  float* out;             // [rows][m]
+  float* carry_out;       // [rows][L - 1]: the tail after this piece, not carry_in
+  int64_t rows, n, pitch, m;
+  int carry_len, skip;    // skip: raw samples before the next output's support (D > L only; then carry_len = 0)
+  int D, L;
+};
+// outputs that a piece of n raw samples completes
+int64_t fir_output_count(int64_t carry_len, int64_t skip, int64_t n, int L, int D);
+// -2 unless 1 <= D <= 64, 1 <= L <= 1025, 0 <= carry_len <= L - 1, skip >= 0, m = fir_output_count(..), every
+// pointer the launch uses is non-null and carry_out is not carry_in
+int launch_fir_decimate(const FirArgs& a, int itype, hipStream_t st);
 // synth.hip: on-device synthetic DAS samples (data/synthetic.py physical model, Philox noise)
 constexpr int SYNTH_NPARAM = 9;  // per sample: distance, event, x0, t0, jitter[4], snr_db
 struct SynthArgs {

@@ -23,6 +23,11 @@ floor by the gate are reported as quiet and only the others are evaluated.
 that became available are evaluated by replays of one graph, and map columns are returned as they become final
 (csrc/live.hip on the engine path, a host ring and the fp32 module elsewhere).  ``LiveRecording(gate_db=...)`` gates
 the stream too: its noise floor runs along with it (:func:`running_floor_reference`; csrc/live_gate.hip).
+
+A recording at the interrogator's raw rate (``decimate=D``, fp32 or int16) is low-pass filtered and decimated first
+(data/resample.py is the definition; csrc/resample.hip on the engine path): :func:`decimate_recording` for a whole
+recording, and in :class:`LiveRecording` piece by piece with the filter's state carried across the pushes, so the
+decimated stream does not depend on how the raw one was cut.
 """
 from __future__ import annotations
 
@@ -167,11 +172,63 @@ def _power_db(power: np.ndarray) -> np.ndarray:
         return 10.0 * np.log10(np.asarray(power, dtype=np.float64))
 
 
+def _raw_recording(rec) -> torch.Tensor:
+    """A raw recording or chunk as a tensor [C, F, T]: int16 stays int16, anything else becomes fp32."""
+    raw = torch.as_tensor(rec)
+    if raw.dim() == 2:
+        raw = raw.unsqueeze(0)
+    if raw.dim() != 3:
+        raise ValueError(f"a recording is [F, T] or [C, F, T], got {tuple(raw.shape)}")
+    return raw if raw.dtype == torch.int16 else raw.float()
+
+
+def _decimation(decimate, taps):
+    """``(D, taps)`` of a ``decimate`` / ``taps`` argument pair, the taps as the fp32 [L] array the filter runs
+    with; ``(None, None)`` without decimation."""
+    if decimate is None:
+        if taps is not None:
+            raise ValueError("taps without decimate")
+        return None, None
+    from .data.resample import as_taps
+    h = as_taps(taps, decimate)
+    return int(decimate), h
+
+
+def _raw_times(res: Dict, D: int, L: int, Wt: int = WINDOW[1]) -> Dict:
+    """The windows' extent in raw samples: ``raw_time_start`` and ``raw_time_stop``, one past the last raw sample
+    the window depends on."""
+    t0 = res["positions"][:, 1]
+    res["raw_time_start"], res["raw_time_stop"] = t0 * D, (t0 + Wt - 1) * D + L
+    return res
+
+
+@torch.no_grad()
+def decimate_recording(rec, D: int, taps=None, device=None, use_engine: Optional[bool] = None) -> torch.Tensor:
+    """The raw recording ``rec`` ([F, T] or [C, F, T], fp32 or int16) through the FIR ``taps`` (None:
+    ``data.resample.decimation_taps(D)``) and decimation by ``D``: fp32 [C, F, K], ``K = (T - L) // D + 1`` (the
+    "valid" form of data/resample.py: no padded edge).  On the engine path the raw recording is uploaded as it is
+    (int16 stays int16), one ``fir_decimate`` launch runs on it and the result stays on the device; elsewhere the
+    fp64 reference, rounded to fp32."""
+    if D is None:
+        raise ValueError("decimate_recording needs a factor D")
+    D, h = _decimation(D, taps)
+    raw = _raw_recording(rec)
+    device = torch.device(device) if device is not None else raw.device
+    if use_engine is None:
+        use_engine = device.type == "cuda"
+    if use_engine:
+        from .ops import functional as HF
+        raw_d = raw.to(device).contiguous()
+        return HF.fir_decimate(raw_d, None, 0, 0, torch.from_numpy(h).to(device), D)[0]
+    from .data.resample import fir_decimate_reference
+    return torch.from_numpy(fir_decimate_reference(raw.cpu().numpy(), h, D).astype(np.float32)).to(device)
+
+
 @torch.no_grad()
 def predict_recording(model: nn.Module, model_type: str, rec: torch.Tensor, stride=(100, 125), batch: int = 32,
                       ctx: Optional[DistContext] = None, device=None, use_engine: Optional[bool] = None,
                       windows: Optional[str] = None, runner=None, gate_db: Optional[float] = None,
-                      noise_floor="auto") -> Dict:
+                      noise_floor="auto", decimate: Optional[int] = None, taps=None) -> Dict:
     """Per-window predictions for one recording.  Returns numpy arrays: ``positions`` [N, 2], and per task
     (``distance`` / ``event`` as the model provides) ``<task>_pred`` [N] and ``<task>_prob`` [N, k].
 
@@ -187,10 +244,21 @@ def predict_recording(model: nn.Module, model_type: str, rec: torch.Tensor, stri
     ``<task>_pred`` -1 (Model C's decoded ``distance_pred`` / ``event_pred`` too) and a zero ``<task>_prob`` row.
     On the resident path power, floor, selection and the evaluation of the selected windows run on the device
     (csrc/gate.hip); every rank computes all flags and gates its own shard.  None: no gate, every window
-    evaluated."""
+    evaluated.
+
+    ``decimate`` = D: ``rec`` is at the raw rate (fp32 or int16) and goes through :func:`decimate_recording` with
+    ``taps`` first; everything else runs on the result as it does without, every rank decimating for itself.  The
+    result gains ``raw_time_start`` = ``positions[:, 1] * D`` and ``raw_time_stop`` =
+    ``(positions[:, 1] + Wt - 1) * D + L``, one past the last raw sample the window depends on.  None: ``rec`` is at
+    the model's rate."""
     device = torch.device(device) if device is not None else (ctx.device if ctx else torch.device("cpu"))
     if use_engine is None:
         use_engine = device.type == "cuda"
+    D, h = _decimation(decimate, taps)
+    if D is not None:
+        res = predict_recording(model, model_type, decimate_recording(rec, D, h, device, use_engine), stride, batch,
+                                ctx, device, use_engine, windows, runner, gate_db, noise_floor)
+        return _raw_times(res, D, len(h))
     if windows is None:
         windows = "resident" if use_engine else "materialize"
     if windows not in ("resident", "materialize"):
@@ -580,11 +648,16 @@ class LiveBook:
 
     def check_push(self, n: int):
         """Raise before anything is written if a step of this push would overwrite live rows of the table."""
+        self.check_steps(self.split(n))
+
+    def check_steps(self, steps):
+        """:meth:`check_push` for appends of ``steps`` samples in turn (a decimated push appends what each raw piece
+        yields)."""
         if self.flushed:
             raise RuntimeError("push after flush")
         total, j_done, q_done = self.total, self.j_done, self.q_done
         try:
-            for m in self.split(n):
+            for m in steps:
                 self.advance(m)
         finally:
             self.total, self.j_done, self.q_done = total, j_done, q_done
@@ -666,6 +739,18 @@ class _TorchLive:
 
     def flush(self):
         pass
+
+    def set_decimation(self, taps: np.ndarray, D: int, raw_step: int):
+        from .data.resample import HostDecimator
+        self.decimator = HostDecimator(taps, D)  # carries the raw samples on the host, in fp64
+
+    def append_raw(self, piece: torch.Tensor, m: int, carry_len: int, skip: int):
+        """A raw piece through the fp64 reference; the ``m`` outputs it completes, rounded to fp32, are appended."""
+        y = self.decimator.push(piece.detach().cpu().numpy())
+        if y.shape[-1] != m:
+            raise AssertionError("the decimator and the recording's book disagree")
+        if m:
+            self.append(torch.from_numpy(y.astype(np.float32)))
 
     def _flags(self, starts):
         """The gate of the new windows by the fp64 references: (active, power, floor), each [m * nf] in number
@@ -781,6 +866,41 @@ class _EngineLive:
     def flush(self):
         self.HF.ring_append(self.ring, self.state, None, len(self.fs), self.st, self.window[1], flush=True)
 
+    def set_decimation(self, taps: np.ndarray, D: int, raw_step: int):
+        """The raw front end: the taps, the two carry buffers a launch reads and writes in turn, and one pinned raw
+        staging buffer with its device twin for pieces of at most ``raw_step`` raw samples per row (bytes: an fp32
+        or an int16 piece is staged as it is)."""
+        C, Fn, _ = self.ring.shape
+        dev = self.ring.device
+        self.D, self.taps_d = D, torch.from_numpy(taps).to(dev)
+        self.carry, self.cur = self.HF.decimate_carry(C * Fn, len(taps), dev), 0
+        self.raw_h = torch.empty(4 * C * Fn * raw_step, dtype=torch.uint8).pin_memory()
+        self.raw_d = torch.empty(4 * C * Fn * raw_step, dtype=torch.uint8, device=dev)
+        self.raw_staged = None  # event: the last upload from raw_h has finished
+
+    def append_raw(self, piece: torch.Tensor, m: int, carry_len: int, skip: int):
+        """A raw piece [C, F, n] (fp32 or int16) -> fir_decimate -> the decimated staging buffer -> ring_append.  A
+        piece on the device is read where it is; one on the host goes through the raw staging buffers."""
+        C, Fn, n = piece.shape
+        if piece.is_cuda:
+            raw = piece
+        else:
+            if self.raw_staged is not None:
+                self.raw_staged.synchronize()  # the buffer is being read until then
+            cnt = C * Fn * n
+            src = self.raw_h.view(piece.dtype)[:cnt].view(C, Fn, n)
+            src.copy_(piece)
+            raw = self.raw_d.view(piece.dtype)[:cnt].view(C, Fn, n)
+            raw.copy_(src, non_blocking=True)
+            self.raw_staged = torch.cuda.Event()
+            self.raw_staged.record()
+        dst = self.stage_d[:C * Fn * m].view(C, Fn, m)
+        self.HF.fir_decimate(raw, self.carry[self.cur], carry_len, skip, self.taps_d, self.D, out=dst, m=m,
+                             carry_out=self.carry[1 - self.cur])
+        self.cur = 1 - self.cur
+        if m:
+            self.HF.ring_append(self.ring, self.state, dst, len(self.fs), self.st, self.window[1])
+
     def evaluate(self, starts):
         """As :meth:`_TorchLive.evaluate`.  Gated: power, floor and selection of the new windows are launched eagerly
         (the range is the host's, LiveBook's), the count is read once (8 bytes) and the graph replayed
@@ -856,15 +976,29 @@ class LiveRecording:
     ``predict_recording(rec, gate_db=..., noise_floor=P)`` and its map on the concatenated chunks.  On the engine
     backend power, floor and the ordered selection of each appended piece run on the device (csrc/live_gate.hip), the
     count of active windows is read back once per piece and the one graph replayed ceil(count / batch) times.  None:
-    no gate, every window evaluated."""
+    no gate, every window evaluated.
+
+    ``decimate`` = D: ``push`` takes **raw** chunks ``[C, F, n_raw]`` (fp32 or int16, host or device), which go
+    through the FIR ``taps`` (None: ``data.resample.decimation_taps(D)``) and decimation by D ahead of the ring
+    (:func:`decimate_recording` is the whole-recording form); ``stride``, ``cell``, ``ring``, ``table_indices``,
+    ``floor_history`` and ``total`` stay in decimated samples, as the model sees them.  The chunk is processed in raw
+    pieces that each yield at most ``ring - window`` outputs; the raw samples that the next output still needs (at
+    most L - 1 per row) are carried across pieces and pushes, on the engine backend on the device
+    (csrc/resample.hip; ``DecimatorBook`` mirrors the counts on the host), so the decimated stream -- and with it
+    every result -- has the same bits however the raw stream is cut.  A push that completes no output returns an
+    empty result; ``flush()`` drops the carried raw samples.  The results gain ``raw_time_start`` /
+    ``raw_time_stop`` as :func:`predict_recording`'s.  None: chunks are at the model's rate."""
+
+    RAW_PIECE = 1 << 24  # raw elements staged per piece at most (and never below one decimation's D per row)
 
     def __init__(self, model: nn.Module, model_type: str, F: int, C: int = 1, stride=(100, 125), cell=None,
                  ring: int = 8 * WINDOW[1], batch: int = 32, device=None, use_engine: Optional[bool] = None,
                  ctx: Optional[DistContext] = None, table_indices: Optional[int] = None, window=WINDOW,
                  gate_db: Optional[float] = None, noise_floor="running", floor_history: int = 64,
-                 floor_warmup: int = 8):
+                 floor_warmup: int = 8, decimate: Optional[int] = None, taps=None):
         if ctx is not None and ctx.enabled and ctx.world > 1:
             raise ValueError("a live recording is not sharded: world > 1 is not supported")
+        self.decimate, self.taps = _decimation(decimate, taps)
         self.gate = None
         if gate_db is not None:
             self.gate = _live_gate(gate_db, noise_floor, floor_history, floor_warmup)
@@ -889,6 +1023,13 @@ class LiveRecording:
         self.backend = backend(model, model_type, self.C, self.F, int(ring), self.fs, self.window, self.stride[1],
                                self.book.jcap, K, batch, device, **({} if self.gate is None else {"gate": self.gate}))
         self.backend.cf = self.cell[0] if self.cell is not None else None
+        if self.decimate is not None:
+            from .data.resample import DecimatorBook
+            self.dbook = DecimatorBook(len(self.taps), self.decimate)
+            # n raw samples complete at most (n - 1) // D + 1 outputs: a piece of (R - Wt) D fits one append
+            per_row = max(self.decimate, self.RAW_PIECE // (self.C * self.F))
+            self.raw_step = min((int(ring) - self.window[1]) * self.decimate, per_row)
+            self.backend.set_decimation(self.taps, self.decimate, self.raw_step)
 
     @property
     def total(self) -> int:
@@ -914,6 +1055,8 @@ class LiveRecording:
                                     for i, dt in enumerate((bool, np.float64, np.float64)))
             flags = (active, power)
         res = _result(self.model_type, self.names, probs, pos, None, flags)
+        if self.decimate is not None:
+            _raw_times(res, self.decimate, len(self.taps), self.window[1])
         if gated:
             res["floor_db"] = _power_db(floor)
         if self.cell is not None:
@@ -944,6 +1087,8 @@ class LiveRecording:
             chunk = chunk.unsqueeze(0)
         if chunk.dim() != 3 or chunk.shape[0] != self.C or chunk.shape[1] != self.F or chunk.shape[2] < 1:
             raise ValueError(f"a chunk must be [{self.C}, {self.F}, n >= 1], got {tuple(chunk.shape)}")
+        if self.decimate is not None:
+            return self._push_raw(chunk)
         n = chunk.shape[2]
         self.book.check_push(n)
         rows, starts, maps, q_first, at = [], [], [], self.book.q_done, 0
@@ -951,6 +1096,34 @@ class LiveRecording:
             (j0, j1), (q0, q1) = self.book.advance(m)
             self.backend.append(chunk[:, :, at:at + m].float())
             at += m
+            new = [(j, self.book.time_start(j)) for j in range(j0, j1)]
+            rows.append(self.backend.evaluate(new))
+            starts += new
+            if self.cell is not None:
+                maps.append(self._emit(q0, q1, None))
+        return self._result(rows, starts, q_first, maps)
+
+    def _push_raw(self, chunk: torch.Tensor) -> Dict:
+        """``push`` of a raw chunk: raw pieces of at most ``raw_step`` samples, each decimated into the staging
+        buffer and, if it completes outputs, appended and evaluated as a chunk of ``push`` is."""
+        chunk = _raw_recording(chunk)
+        if chunk.is_cuda and not chunk.is_contiguous():
+            chunk = chunk.contiguous()
+        n = chunk.shape[2]
+        sizes = [min(self.raw_step, n - i) for i in range(0, n, self.raw_step)]
+        plan = self.dbook.plan(sizes)
+        outputs = sum(p[0] for p in plan)
+        if outputs:  # before anything is written: the push as a whole, and as the appends it will make
+            self.book.check_push(outputs)
+            self.book.check_steps([p[0] for p in plan if p[0]])
+        rows, starts, maps, q_first, at = [], [], [], self.book.q_done, 0
+        for size in sizes:
+            m, carry_len, skip = self.dbook.push(size)
+            self.backend.append_raw(chunk[:, :, at:at + size], m, carry_len, skip)
+            at += size
+            if m == 0:
+                continue
+            (j0, j1), (q0, q1) = self.book.advance(m)
             new = [(j, self.book.time_start(j)) for j in range(j0, j1)]
             rows.append(self.backend.evaluate(new))
             starts += new

@@ -1174,3 +1174,77 @@ def live_map(table: torch.Tensor, fs, F: int, Wf: int, cf: int, jcap: int, jlo, 
                               "Wf": Wf, "cf": cf, "nfc": nfc, "Jcap": int(jcap), "nrows": N},
                    fs_h, [int(v) for v in jlo], jn)
     return out
+
+
+# ---- raw-rate recordings: FIR and decimation ahead of the ring (csrc/resample.hip) ------------------------------
+DECIMATE_TILE = 128  # outputs of one block; must match csrc/kernels.h
+
+
+def decimate_carry(rows: int, L: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The two carry buffers of a decimated stream, fp32 [rows, L - 1] each: a launch reads one and writes the
+    other, and the host flips them."""
+    return (torch.zeros(rows, L - 1, device=device), torch.zeros(rows, L - 1, device=device))
+
+
+def fir_decimate(raw: torch.Tensor, carry_in: Optional[torch.Tensor], carry_len: int, skip: int, taps: torch.Tensor,
+                 D: int, out: Optional[torch.Tensor] = None, m: Optional[int] = None,
+                 carry_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """One piece of a raw stream through the FIR ``taps`` (fp32 [L]) and decimation by ``D``
+    (data/resample.py ``fir_decimate_reference`` is the definition).  ``raw``: [C, F, n] fp32 or int16, time
+    contiguous (a slice along time of a contiguous tensor will do).  The piece's samples are the first
+    ``carry_len`` columns of ``carry_in`` (fp32 [C * F, L - 1]; None: nothing carried) followed by ``raw[.., skip:]``;
+    ``out`` (fp32 [C, F, m], the layout :func:`ring_append` takes) gets the ``m`` outputs they complete and
+    ``carry_out`` (not ``carry_in``) the new tail, in its first columns -- ``DecimatorBook`` says how many.  Every
+    output is one fp32 fma chain over the taps in a fixed order, so a stream has the same bits however it is cut.
+    ``m``: checked against the count the other arguments imply (None: that count).  Returns ``(out, carry_out)``."""
+    if raw.dim() != 3:
+        raise ValueError(f"raw must be [C, F, n], got {tuple(raw.shape)}")
+    if not raw.is_cuda:
+        raise RuntimeError("HIP ops need a GPU tensor")
+    if raw.dtype not in (torch.float32, torch.int16):
+        raise TypeError(f"raw must be float32 or int16, got {raw.dtype}")
+    _check(taps, torch.float32)
+    C, Fn, n = raw.shape
+    rows, L, D = C * Fn, taps.numel(), int(D)
+    if taps.dim() != 1 or not 1 <= L <= lib().DECIMATE_MAX_TAPS or not 1 <= D <= lib().DECIMATE_MAX_FACTOR:
+        raise ValueError(f"1 <= D <= {lib().DECIMATE_MAX_FACTOR} and 1 <= L <= {lib().DECIMATE_MAX_TAPS} taps, got "
+                         f"D = {D}, taps {tuple(taps.shape)}")
+    if rows < 1:
+        raise ValueError("raw has no rows")
+    pitch = n
+    if n > 0:
+        pitch = raw.stride(1) if Fn > 1 else (raw.stride(0) if C > 1 else n)
+        if raw.stride(2) != 1 or pitch < n or (C > 1 and raw.stride(0) != Fn * pitch):
+            raise ValueError("raw must be contiguous along time with one row pitch")
+    carry_len, skip = int(carry_len), int(skip)
+    if not 0 <= carry_len <= L - 1 or skip < 0 or (skip > 0 and carry_len > 0):
+        raise ValueError(f"0 <= carry_len <= L - 1 = {L - 1} and skip >= 0 (and nothing carried), got carry_len "
+                         f"{carry_len}, skip {skip}")
+    want = lib().fir_output_count(carry_len, skip, n, L, D)
+    if m is None:
+        m = want
+    if int(m) != want:
+        raise ValueError(f"a piece of {n} samples after a carry of {carry_len} and a skip of {skip} yields {want} "
+                         f"outputs, not {m}")
+    m = int(m)
+    for name, c in (("carry_in", carry_in), ("carry_out", carry_out)):
+        if c is not None:
+            _check(c, torch.float32)
+            if tuple(c.shape) != (rows, L - 1):
+                raise ValueError(f"{name} must be [{rows}, {L - 1}], got {tuple(c.shape)}")
+    if carry_len > 0 and carry_in is None:
+        raise ValueError("carry_len > 0 without carry_in")
+    if carry_out is None:
+        carry_out = torch.zeros(rows, L - 1, device=raw.device)
+    if carry_in is not None and L > 1 and carry_in.data_ptr() == carry_out.data_ptr():
+        raise ValueError("carry_out must not be carry_in: a block reads the one while another writes the other")
+    if out is None:
+        out = torch.empty(C, Fn, m, device=raw.device)
+    _check(out, torch.float32)
+    if tuple(out.shape) != (C, Fn, m):
+        raise ValueError(f"out must be [{C}, {Fn}, {m}], got {tuple(out.shape)}")
+    lib().fir_decimate(stream(), {"raw": ptr(raw) if n else 0, "carry_in": ptr(carry_in) if carry_in is not None else 0,
+                                  "taps": ptr(taps), "out": ptr(out) if m else 0, "carry_out": ptr(carry_out),
+                                  "rows": rows, "n": n, "pitch": pitch, "m": m, "carry_len": carry_len, "skip": skip,
+                                  "D": D, "L": L, "itype": 1 if raw.dtype == torch.int16 else 0})
+    return out, carry_out

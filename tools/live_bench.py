@@ -8,6 +8,13 @@ fiber has fewer windows than the batch) and for a chunk of 2,000 samples, from t
 and with the map; then ``predict_recording`` on a kept ``window_runner`` and a ``LiveRecording`` stream on the same
 recording.  Host clock around calls that end in the device-to-host copy of their results, synchronised before and
 after, each size after untimed calls of the same size.  Prints one JSON line.
+
+    python tools/live_bench.py --decimate 10
+
+adds ``decimate``: the ``fir_decimate`` launch alone on 2,000 * D raw samples per row (fp32 and int16 input; the
+default taps and ``taps = [1]``) beside a device-to-device copy of the same raw bytes timed in the same run -- every
+raw sample has to be read once, so the copy is the floor -- and ``LiveRecording.push`` of that raw chunk from the host
+beside a push of the 2,000 decimated samples without decimation.
 """
 import argparse
 import json
@@ -26,6 +33,7 @@ def main():
     ap.add_argument("--stride", default="100,125")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--ring", type=int, default=4096)
+    ap.add_argument("--decimate", type=int, default=None, help="also time the raw-rate front end at this factor")
     args = ap.parse_args()
     import torch
     from mtl_das_pytorch_amd.inference import WINDOW, LiveRecording, predict_recording, window_runner
@@ -94,7 +102,53 @@ def main():
     ts = timed(lambda: cnts.append(stream()), 5)
     out["live_stream"] = dict(stats(ts), windows=cnts[-1], windows_per_s=round(cnts[-1] / statistics.median(ts), 1))
     live.close()
+    if args.decimate is not None:
+        out["decimate"] = decimate_timings(args, m, stride, timed, stats)
     print(json.dumps(out))
+
+
+def decimate_timings(args, model, stride, timed, stats):
+    """The raw-rate front end at factor ``--decimate``: launch, copy floor and push (module docstring)."""
+    import torch
+    from mtl_das_pytorch_amd.data.resample import as_taps
+    from mtl_das_pytorch_amd.inference import LiveRecording
+    from mtl_das_pytorch_amd.ops import functional as HF
+    D, F, n_out = args.decimate, args.fiber, 2000
+    g = torch.Generator().manual_seed(2)
+    res = {"D": D, "fiber": F, "raw_per_row": n_out * D}
+    raws = {"fp32": torch.randn(1, F, n_out * D, generator=g),
+            "int16": torch.randint(-3000, 3000, (1, F, n_out * D), generator=g).to(torch.int16)}
+    for name, taps in (("default", as_taps(None, D)), ("one", as_taps([1.0], D))):
+        taps_d = torch.from_numpy(taps).cuda()
+        for kind, raw in raws.items():
+            raw_d = raw.cuda()
+            m = (raw_d.shape[2] - len(taps)) // D + 1
+            dst = torch.empty(1, F, m, device="cuda")
+            carry = HF.decimate_carry(F, len(taps), "cuda")
+            for _ in range(5):
+                HF.fir_decimate(raw_d, carry[0], 0, 0, taps_d, D, out=dst, m=m, carry_out=carry[1])
+            ts = timed(lambda: HF.fir_decimate(raw_d, carry[0], 0, 0, taps_d, D, out=dst, m=m, carry_out=carry[1]), 50)
+            res[f"launch_{name}_{kind}"] = dict(stats(ts), taps=len(taps), outputs=m)
+    for kind, raw in raws.items():
+        raw_d, twin = raw.cuda(), torch.empty_like(raw, device="cuda")
+        for _ in range(5):
+            twin.copy_(raw_d)
+        res[f"copy_{kind}"] = dict(stats(timed(lambda: twin.copy_(raw_d), 50)), bytes=raw.numel() * raw.element_size())
+    # push from the host: the raw chunk with the front end, and its 2,000 decimated samples without
+    big_n = n_out - n_out % stride[1]
+    live_kw = dict(stride=stride, ring=args.ring, batch=args.batch, device="cuda", use_engine=True)
+    plain = torch.randn(1, F, big_n, generator=g)
+    runs = [("push_plain", {}, plain)]
+    runs += [(f"push_raw_{kind}", {"decimate": D}, raw[:, :, :big_n * D].contiguous()) for kind, raw in raws.items()]
+    for tag, kw, chunk in runs:
+        live = LiveRecording(model, args.model, F, **live_kw, **kw)
+        for _ in range(4):
+            live.push(chunk)
+        nwin = []
+        ts = timed(lambda: nwin.append(len(live.push(chunk)["positions"])), 20)
+        res[tag] = dict(stats(ts), windows=nwin[-1], samples=chunk.shape[2])
+        live.close()
+    return res
 
 
 if __name__ == "__main__":
