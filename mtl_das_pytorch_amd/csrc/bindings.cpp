@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "wgrad_tile.h"
 
 namespace py = pybind11;
 using namespace mda;
@@ -229,6 +230,16 @@ WgradArgs parse_wgrad(const py::dict& d) {
   }
   return a;
 }
+
+// the config table's rows (cfg, family, TN, TK, MCH, CB, W8, R) and the host check on an argument dict: what
+// ops/functional.py WGRAD_CONFIGS / wgrad_ntiles copy, compared by tests/test_wgrad_configs.py (no pointer is read)
+py::list wgrad_configs() {
+  py::list rows;
+  for (const WgradShape& s : WGRAD_SHAPES) rows.append(py::make_tuple(s.cfg, s.family, s.TN, s.TK, s.MCH, s.CB, s.W8, s.R));
+  return rows;
+}
+
+int wgrad_ntiles_of(int cfg, py::dict d) { return wgrad_ntiles(cfg, parse_wgrad(d)); }
 
 void wgrad_finalize(int64_t descs, int nd, int64_t nblocks, double scale, int64_t stream) {
   check(launch_wgrad_finalize(reinterpret_cast<const WgFinDesc*>(static_cast<intptr_t>(descs)), nd, nblocks,
@@ -675,6 +686,8 @@ PYBIND11_MODULE(_mda_hip, m) {
   m.attr("DECIMATE_MAX_FACTOR") = DECIMATE_MAX_FACTOR;
   m.attr("DECIMATE_MAX_TAPS") = DECIMATE_MAX_TAPS;
   m.def("wgrad_table", &wgrad_table);
+  m.def("wgrad_configs", &wgrad_configs);
+  m.def("wgrad_ntiles", &wgrad_ntiles_of);
   m.def("wgrad_batched", &wgrad_batched, py::arg("cfg"), py::arg("table"), py::arg("nj"), py::arg("nblocks"),
         py::arg("stream"), py::arg("cap") = 0);
   m.def("synth_das", &synth_das);

@@ -25,20 +25,12 @@
 // k-group to (segment, kh, kw, channel) so two-segment inputs (cat[F_shared, B_task]) need no concat.
 //
 // The pieces conv_igemm shares with the LDS-staged kernels of conv_lds.hip / conv_patch.hip (BN-backward
-// constants, dz statistics, statistics flush) and the 8-wide normalise-on-load transform of the weight-gradient
-// staging are in conv_tile.h.
-#include "conv_tile.h"
+// constants, dz statistics, statistics flush), the k-group encoder and the 8-wide normalise-on-load transform of the
+// weight-gradient staging are in conv_tile.h; the weight-gradient config table, its dispatch and the kernel entry
+// points in wgrad_tile.h.
+#include "wgrad_tile.h"
 
 namespace mda {
-
-DEV int encode_kg(int i, int Ktot, int Cs8, int KW, int C0) {
-  if (i * 8 >= Ktot) return 0;
-  int tap = i / Cs8, c = (i - tap * Cs8) * 8;
-  int kh = tap / KW, kw = tap - kh * KW;
-  int seg = c >= C0;
-  if (seg) c -= C0;
-  return c | (kw << 14) | (kh << 21) | (seg << 28) | (1 << 29);
-}
 
 // Normalise-on-load: the 8 channels [c, c+8) of an im2col fragment are pre-BN conv outputs y; the operand
 // is act(y * scale + shift) (act = ReLU or identity), rounded to bf16 exactly as the BN tail that used to
@@ -531,38 +523,12 @@ DEV void wgrad_block(const WgradArgs& a, const int tile, const int split, const 
 }
 
 template <int TN, int TK, int MCH>
-__global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
-  wgrad_block<TN, TK, MCH>(a, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-
-// Horizontally batched weight gradients: every conv of a backward pass that uses this tile config, in
-// ONE launch.  The weight gradient of a layer only needs its dy and forward input, both resident until
-// the step ends, so all of them are deferred to the end of the backward pass; the ~40 (Model A) / ~90
-// (Model C) small launches become <= 8 large ones that fill the 256 CUs (the deep, small-M layers run
-// side by side instead of one after another).  Block -> job by binary search over the jobs' first blocks.
-// The batched launches walk nvb virtual blocks with a grid of at most nvb hardware blocks: a side stream's
-// batch may run on a capped, persistent grid (launch_wgrad_batched ``cap``), so that it never fills every CU
-// slot while the critical data-gradient chain needs blocks (tools/kernel_phases.py: chain kernels waited up
-// to 16 us for their blocks to start beside an uncapped batch).
-#define WGRAD_FOR_VBLOCKS(BODY)                                                                            \
-  for (int64_t vb = blockIdx.x; vb < nvb; vb += gridDim.x) {                                            \
-    int lo = 0, hi = nj - 1;                                                                               \
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (jobs[mid].block0 <= vb) lo = mid; else hi = mid - 1; } \
-    const WgradJob& J = jobs[lo];                                                                          \
-    const int local = (int)(vb - J.block0);                                                                \
-    const int per_z = J.ntiles * J.a.splits;                                                               \
-    const int z = local / per_z, r = local - z * per_z;                                                    \
-    BODY;                                                                                                  \
-    __syncthreads(); /* the next virtual block re-stages the LDS tiles */                                  \
-  }
-
-template <int TN, int TK, int MCH>
-__global__ __launch_bounds__(256) void conv_wgrad_batched_kernel(const WgradJob* __restrict__ jobs, int nj, int64_t nvb) {
-  WGRAD_FOR_VBLOCKS((wgrad_block<TN, TK, MCH>(J.a, r % J.ntiles, r / J.ntiles, z)))
+DEV void WgTile<TN, TK, MCH>::run(const WgradArgs& a, int tile, int split, int z) {
+  wgrad_block<TN, TK, MCH>(a, tile, split, z);
 }
 
 // ------------------------------------------------------------------------------------------------
-// Large-tile weight gradient on the 32x32x16 MFMA (configs WGRAD_BIG_CFG0 + i).  The 16-32-wide tiles of
+// Large-tile weight gradient on the 32x32x16 MFMA (configs 32-35).  The 16-32-wide tiles of
 // wgrad_block re-stage dy and the im2col operand once per tile: Model C's wide 1x7 / 7x1 layers staged
 // ~1.2 GB per step through LDS for ~50 GFLOP, at one 16x16x32 MFMA per two transposed reads.  Here a
 // block owns a TN x TK tile of 64 or 128 rows / columns, its 4 waves a (TN/2) x (TK/2) quarter each, a
@@ -636,13 +602,8 @@ DEV void wgrad_big_block(const WgradArgs& a, const int tile, const int split, co
 }
 
 template <int TN, int TK>
-__global__ __launch_bounds__(256) void conv_wgrad_big_kernel(WgradArgs a) {
-  wgrad_big_block<TN, TK>(a, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-
-template <int TN, int TK>
-__global__ __launch_bounds__(256) void conv_wgrad_big_batched_kernel(const WgradJob* __restrict__ jobs, int nj, int64_t nvb) {
-  WGRAD_FOR_VBLOCKS((wgrad_big_block<TN, TK>(J.a, r % J.ntiles, r / J.ntiles, z)))
+DEV void WgBig<TN, TK>::run(const WgradArgs& a, int tile, int split, int z) {
+  wgrad_big_block<TN, TK>(a, tile, split, z);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -655,8 +616,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_big_batched_kernel(const Wgrad
 // a job covers units [s * m_per_split, ...).  Tile = (TN output channels) x (all 9 taps x CB input
 // channels), written to the same [split][Npad][Kpad] slab layout as the im2col kernel (k = tap*Cs + ci).
 // R = 2 strips for the wide (W8 = 128) stem maps keep the staging registers and LDS within 2 blocks per CU.
+// (The block function is WgPatch's run itself: called through a forwarding run like the other families', the patch
+// kernels came out with other instruction counts and one of them with 2 VGPRs less.)
 template <int TN, int CB, int W8, int R>
-DEV void wgrad_patch_block(const WgradArgs& a, const int tile, const int split, const int z) {
+DEV void WgPatch<TN, CB, W8, R>::run(const WgradArgs& a, const int tile, const int split, const int z) {
   constexpr int TAPS = 9;
   constexpr int CBP = CB + 8, LDY = TN + 8, WP = W8 + 2;
   constexpr int FN = TN / 16, FC = CB / 16, NFR = FN * TAPS * FC, FPW = (NFR + 3) / 4;
@@ -781,16 +744,6 @@ DEV void wgrad_patch_block(const WgradArgs& a, const int tile, const int split, 
         if (row + q < a.Npad) slab[(int64_t)(row + q) * a.Kpad + col] = acc[j][q];
     }
   }
-}
-
-template <int TN, int CB, int W8, int R>
-__global__ __launch_bounds__(256) void conv_wgrad_patch_kernel(WgradArgs a) {
-  wgrad_patch_block<TN, CB, W8, R>(a, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-
-template <int TN, int CB, int W8, int R>
-__global__ __launch_bounds__(256) void conv_wgrad_patch_batched_kernel(const WgradJob* __restrict__ jobs, int nj, int64_t nvb) {
-  WGRAD_FOR_VBLOCKS((wgrad_patch_block<TN, CB, W8, R>(J.a, r % J.ntiles, r / J.ntiles, z)))
 }
 
 // Sums the split-M partial slabs of many convolutions into the flat fp32 gradient buffer (deterministic,
@@ -951,147 +904,53 @@ int launch_conv(int mode, const ConvArgs& a0, int G, int cfg, hipStream_t st) {
   return a.bpart ? launch_conv_cfg<MODE_DGRAD_BNS>(a, G, cfg, st) : launch_conv_cfg<MODE_DGRAD>(a, G, cfg, st);
 }
 
-// Weight-gradient tile configurations (TN = output channels, TK = reduction columns, MCH = pixels per
-// LDS chunk); keep in sync with wgrad_tile_shape and ops/functional.py WGRAD_TILES.  Configs 8-11 cover
-// the whole reduction of a small-Cout layer in one tile: dy is read once per pixel and the im2col taps
-// of neighbouring pixels re-hit L1, instead of every 32-wide K tile re-reading dy and its im2col slice
-// from L2 (Model A's 16-channel 33x83 layers moved ~50 MB of L2 traffic each with TK = 32).
-#define WGRAD_CFG_CASES(X)                                                                          \
-  case 0: X(16, 32, 128) case 1: X(32, 32, 128) case 2: X(32, 64, 64) case 3: X(64, 64, 64)         \
-  case 4: X(16, 64, 128) case 5: X(16, 32, 256) case 6: X(32, 32, 256) case 7: X(64, 32, 64)        \
-  case 8: X(16, 192, 64) case 9: X(16, 128, 64) case 10: X(32, 192, 64) case 11: X(32, 320, 32)
-
-// Patch configs 12-19 (TN, CB, max padded output width, strip rows); keep in sync with ops/functional.py
-// WGRAD_PATCH.
-#define WGRAD_PATCH_CASES(X)                                                                       \
-  case 12: X(16, 16, 88, 4) case 13: X(32, 16, 88, 4) case 14: X(32, 32, 48, 4) case 15: X(64, 32, 24, 4) \
-  case 16: X(32, 32, 128, 2) case 17: X(64, 32, 128, 2) case 18: X(64, 16, 128, 2) case 19: X(32, 16, 128, 2)
-
-// Large-tile configs 32-35 (TN, TK; 64-pixel chunks); keep in sync with ops/functional.py WGRAD_BIG.
-#define WGRAD_BIG_CASES(X) case 32: X(64, 64) case 33: X(64, 128) case 34: X(128, 64) case 35: X(128, 128)
-
-int wgrad_big_shape(int cfg, int& TN, int& TK) {
-  if (cfg < WGRAD_BIG_CFG0 || cfg >= WGRAD_BIG_CFG0 + WGRAD_BIG_NCFG) return -1;
-  const int k = cfg - WGRAD_BIG_CFG0;
-  TN = (k & 2) ? 128 : 64;
-  TK = (k & 1) ? 128 : 64;
-  return 0;
-}
-
-int wgrad_patch_shape(int cfg, int& TN, int& CB, int& W8, int& R) {
-  static const int tn[] = {16, 32, 32, 64, 32, 64, 64, 32}, cb[] = {16, 16, 32, 32, 32, 32, 16, 16};
-  static const int w8[] = {88, 88, 48, 24, 128, 128, 128, 128}, rr[] = {4, 4, 4, 4, 2, 2, 2, 2};
-  if (cfg < WGRAD_PATCH_CFG0 || cfg >= WGRAD_PATCH_CFG0 + WGRAD_PATCH_NCFG) return -1;
-  const int k = cfg - WGRAD_PATCH_CFG0;
-  TN = tn[k]; CB = cb[k]; W8 = w8[k]; R = rr[k];
-  return 0;
-}
-
+// Tiles per group of a weight-gradient launch, and the one host check of every family: -1 no such config, -2 the
+// config cannot take this conv -- its tiles do not cover it, or a value its kernel packs into a bit field or a
+// 32-bit offset would not fit.  Every launcher calls it first; ops/functional.py wgrad_ntiles mirrors it.
 int wgrad_ntiles(int cfg, const WgradArgs& a) {
-  if (cfg >= WGRAD_LEAN_CFG0 && cfg < WGRAD_LEAN_CFG0 + WGRAD_LEAN_NCFG) return wgrad_lean_ntiles(cfg, a);
-  int TN, TK, CB, W8, R;
-  if (!wgrad_patch_shape(cfg, TN, CB, W8, R)) {
+  WgradShape s;
+  if (!wgrad_shape(cfg, s)) return -1;
+  const int tn = (a.Npad + s.TN - 1) / s.TN;
+  if (s.family == WG_PATCH) {
     const int Wo8 = (a.Wo + 7) & ~7;
-    const bool seg_ok = a.src.C1 == 0 || a.src.C0 % CB == 0;
+    const bool seg_ok = a.src.C1 == 0 || a.src.C0 % s.CB == 0;
     if (a.KH != 3 || a.KW != 3 || a.sh != 1 || a.sw != 1 || a.ph > 1 || a.pw > 1 || a.ph < 0 || a.pw < 0 ||
-        a.Ho != a.Hi + 2 * a.ph - 2 || a.Wo != a.Wi + 2 * a.pw - 2 || a.Cs % CB || Wo8 > W8 || (R * Wo8) % 32 ||
-        !seg_ok || a.Kpad < 9 * a.Cs)
+        a.Ho != a.Hi + 2 * a.ph - 2 || a.Wo != a.Wi + 2 * a.pw - 2 || a.Cs % s.CB || Wo8 > s.W8 ||
+        (s.R * Wo8) % 32 || !seg_ok || a.Kpad < 9 * a.Cs)
       return -2;
-    return ((a.Npad + TN - 1) / TN) * (a.Cs / CB);
+    return tn * (a.Cs / s.CB);
   }
-  if (!wgrad_big_shape(cfg, TN, TK)) return ((a.Npad + TN - 1) / TN) * ((a.Kpad + TK - 1) / TK);
-  if (wgrad_tile_shape(cfg, TN, TK) || a.Kpad % TK) return -2;  // the K tiles must cover Kpad exactly
-  return ((a.Npad + TN - 1) / TN) * (a.Kpad / TK);
+  if (!kg_fits(a.Cs, a.src.C0, a.KH, a.KW)) return -2;
+  if (s.family == WG_SMALL || s.family == WG_WHOLE) return a.Kpad % s.TK ? -2 : tn * (a.Kpad / s.TK);
+  if (s.family == WG_LEAN || s.family == WG_LEANBIG) {
+    // lean staging: fdiv24's exact range, 32-bit offsets, the pixel table's 16-bit row / column with taps added
+    // as 7-bit fields, and the dy channels of the last row tile in LEAN_CH_BITS
+    const int64_t M = (int64_t)a.B * a.Ho * a.Wo;
+    const int64_t xin = (int64_t)a.B * a.Hi * a.Wi;
+    const int64_t ld = std::max(a.src.ld[0], a.src.C1 > 0 ? a.src.ld[1] : 0);
+    if (!(M < (1 << 24) && xin * ld < ((int64_t)1 << 31) && M * a.ldd < ((int64_t)1 << 31) && a.Wi < 32768 &&
+          a.Hi < 16384 && a.KH < 128 && a.KW < 128 && tn * s.TN - 8 < (1 << LEAN_CH_BITS)))
+      return -2;
+  }
+  return tn * ((a.Kpad + s.TK - 1) / s.TK);
 }
 
 int launch_wgrad(const WgradArgs& a, int G, int cfg, hipStream_t st) {
-  if (cfg >= WGRAD_LEAN_CFG0 && cfg < WGRAD_LEAN_CFG0 + WGRAD_LEAN_NCFG) return launch_wgrad_lean(a, G, cfg, st);
-  if (cfg >= WGRAD_BIG_CFG0) {
-    const int nt = wgrad_ntiles(cfg, a);
-    if (nt < 0) return nt;
-#define LAUNCH_WGBIG(TN, TK)                                                                            \
-  hipLaunchKernelGGL((conv_wgrad_big_kernel<TN, TK>), dim3(nt, a.splits, G), dim3(256), 0, st, a); \
-  break;
-    switch (cfg) {
-      WGRAD_BIG_CASES(LAUNCH_WGBIG)
-      default: return -1;
-    }
-#undef LAUNCH_WGBIG
+  const int nt = wgrad_ntiles(cfg, a);
+  if (nt < 0) return nt;
+  return wgrad_dispatch(cfg, [&](auto blk) {
+    hipLaunchKernelGGL((wgrad_kernel<decltype(blk)>), dim3(nt, a.splits, G), dim3(256), 0, st, a);
     return (int)hipGetLastError();
-  }
-  if (cfg >= WGRAD_PATCH_CFG0) {
-    const int nt = wgrad_ntiles(cfg, a);
-    if (nt < 0) return nt;
-#define LAUNCH_WGP(TN, CB, W8, R)                                                                      \
-  hipLaunchKernelGGL((conv_wgrad_patch_kernel<TN, CB, W8, R>), dim3(nt, a.splits, G), dim3(256), 0, st, a); \
-  break;
-    switch (cfg) {
-      WGRAD_PATCH_CASES(LAUNCH_WGP)
-      default: return -1;
-    }
-#undef LAUNCH_WGP
-    return (int)hipGetLastError();
-  }
-#define LAUNCH_WG(TN, TK, MCH)                                                                      \
-  {                                                                                                 \
-    dim3 grid(((a.Npad + TN - 1) / TN) * (a.Kpad / TK), a.splits, G);                               \
-    hipLaunchKernelGGL((conv_wgrad_kernel<TN, TK, MCH>), grid, dim3(256), 0, st, a);                \
-    break;                                                                                          \
-  }
-  int TN_, TK_;
-  if (wgrad_tile_shape(cfg, TN_, TK_) || a.Kpad % TK_) return -2;  // the K tiles must cover Kpad exactly
-  switch (cfg) {
-    WGRAD_CFG_CASES(LAUNCH_WG)
-    default: return -1;
-  }
-#undef LAUNCH_WG
-  return (int)hipGetLastError();
-}
-
-int wgrad_tile_shape(int cfg, int& TN, int& TK) {
-  static const int tn[] = {16, 32, 32, 64, 16, 16, 32, 64, 16, 16, 32, 32};
-  static const int tk[] = {32, 32, 64, 64, 64, 32, 32, 32, 192, 128, 192, 320};
-  if (cfg < 0 || cfg >= (int)(sizeof(tn) / sizeof(tn[0]))) return -1;
-  TN = tn[cfg]; TK = tk[cfg];
-  return 0;
+  });
 }
 
 int launch_wgrad_batched(int cfg, const WgradJob* d_jobs, int nj, int64_t nblocks, hipStream_t st, int64_t cap) {
   if (nblocks <= 0) return 0;
-  dim3 grid((unsigned)(cap > 0 && cap < nblocks ? cap : nblocks));
-  if (cfg >= WGRAD_LEAN_CFG0 && cfg < WGRAD_LEAN_CFG0 + WGRAD_LEAN_NCFG)
-    return launch_wgrad_lean_batched(cfg, d_jobs, nj, nblocks, grid, st);
-  if (cfg >= WGRAD_BIG_CFG0) {
-#define LAUNCH_WGBIGB(TN, TK)                                                                                 \
-  hipLaunchKernelGGL((conv_wgrad_big_batched_kernel<TN, TK>), grid, dim3(256), 0, st, d_jobs, nj, nblocks); \
-  break;
-    switch (cfg) {
-      WGRAD_BIG_CASES(LAUNCH_WGBIGB)
-      default: return -1;
-    }
-#undef LAUNCH_WGBIGB
+  const dim3 grid((unsigned)(cap > 0 && cap < nblocks ? cap : nblocks));
+  return wgrad_dispatch(cfg, [&](auto blk) {
+    hipLaunchKernelGGL((wgrad_batched_kernel<decltype(blk)>), grid, dim3(256), 0, st, d_jobs, nj, nblocks);
     return (int)hipGetLastError();
-  }
-  if (cfg >= WGRAD_PATCH_CFG0) {
-#define LAUNCH_WGPB(TN, CB, W8, R)                                                                              \
-  hipLaunchKernelGGL((conv_wgrad_patch_batched_kernel<TN, CB, W8, R>), grid, dim3(256), 0, st, d_jobs, nj, nblocks); \
-  break;
-    switch (cfg) {
-      WGRAD_PATCH_CASES(LAUNCH_WGPB)
-      default: return -1;
-    }
-#undef LAUNCH_WGPB
-    return (int)hipGetLastError();
-  }
-#define LAUNCH_WGB(TN, TK, MCH)                                                                              \
-  hipLaunchKernelGGL((conv_wgrad_batched_kernel<TN, TK, MCH>), grid, dim3(256), 0, st, d_jobs, nj, nblocks); \
-  break;
-  switch (cfg) {
-    WGRAD_CFG_CASES(LAUNCH_WGB)
-    default: return -1;
-  }
-#undef LAUNCH_WGB
-  return (int)hipGetLastError();
+  });
 }
 
 int launch_wgrad_finalize(const WgFinDesc* d_descs, int nd, int64_t nblocks, float scale, hipStream_t st) {

@@ -5,7 +5,8 @@
 //
 //   * the dynamic-LDS layout of each kernel family: ONE function gives the offset of every region and the
 //     total bytes, called by the kernel's carve-up and by its host launcher, so the two cannot disagree;
-//   * prologue: operand base pointers, the BN-backward constants of the fused-statistics data gradient;
+//   * prologue: operand base pointers, the k-group encoder of the im2col kernels (weight gradients included) with
+//     its field widths, the BN-backward constants of the fused-statistics data gradient;
 //   * main loop: accumulator zero, the FN x FM MFMA step (MFMA_STEP), the 8-wide normalise-on-load transform;
 //   * epilogue: the block reduction of the statistics with the fp64 replica atomics, and the output tile of the
 //     LDS-staged kernels (split-K ticket reduction, stores, dz of a BN tail and its three sums).
@@ -72,6 +73,26 @@ DEV ConvBases conv_bases(const ConvArgs& a, int z) {
 // 16 bytes of source pixel (b, ih, iw), channel c of segment seg
 DEV const bf16_t* conv_src(const ConvArgs& a, const ConvBases& s, int seg, int b, int ih, int iw, int c) {
   return (seg ? s.base1 : s.base0) + ((int64_t)(b * a.Hs + ih) * a.Ws + iw) * (seg ? s.ld1 : s.ld0) + c;
+}
+
+// im2col column group i (8 channels of one tap) as conv_igemm and the im2col weight-gradient blocks table it:
+// channel offset within its source segment | kw << 14 | kh << 21 | segment << 28 | valid << 29 (0: the group lies
+// past the reduction -- stages zeros).  The decoders spell the masks out (e & 16383, (e >> 14) & 127).
+constexpr int KG_CH_BITS = 14, KG_TAP_BITS = 7;
+constexpr int KG_KW_SHIFT = KG_CH_BITS, KG_KH_SHIFT = KG_KW_SHIFT + KG_TAP_BITS, KG_SEG_SHIFT = KG_KH_SHIFT + KG_TAP_BITS;
+DEV int encode_kg(int i, int Ktot, int Cs8, int KW, int C0) {
+  if (i * 8 >= Ktot) return 0;
+  int tap = i / Cs8, c = (i - tap * Cs8) * 8;
+  int kh = tap / KW, kw = tap - kh * KW;
+  int seg = c >= C0;
+  if (seg) c -= C0;
+  return c | (kw << KG_KW_SHIFT) | (kh << KG_KH_SHIFT) | (seg << KG_SEG_SHIFT) | (1 << (KG_SEG_SHIFT + 1));
+}
+// host: every value encode_kg packs for this conv fits its field -- the last group's offset in the wider segment
+// (offsets below min(C0, Cs) in segment 0, below Cs - C0 in segment 1) and the last tap's kh, kw
+inline bool kg_fits(int Cs, int C0, int KH, int KW) {
+  const int w0 = C0 < Cs ? C0 : Cs, w1 = Cs - w0;
+  return (w0 > w1 ? w0 : w1) - 8 < (1 << KG_CH_BITS) && KH - 1 < (1 << KG_TAP_BITS) && KW - 1 < (1 << KG_TAP_BITS);
 }
 
 // fused BN statistics: the channels of the tail this data gradient feeds (a concat gradient has more)

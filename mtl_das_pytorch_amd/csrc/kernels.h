@@ -289,17 +289,8 @@ int conv_patch_check(int mode, const ConvArgs& a, int cfg);  // 0, or < 0: the p
 // fp32 workspace floats and ticket count a cfg needs (0 when it does not split K); < 0: cfg invalid for a
 int conv_lds_workspace(int mode, const ConvArgs& a, int G, int cfg, int64_t& ws_floats, int64_t& ntickets);
 int launch_wgrad(const WgradArgs& a, int G, int cfg, hipStream_t st);
-int wgrad_tile_shape(int cfg, int& TN, int& TK);
-constexpr int WGRAD_PATCH_CFG0 = 12, WGRAD_PATCH_NCFG = 8;  // wgrad cfgs 12-19: 3x3/s1 patch kernels (conv.hip)
-constexpr int WGRAD_BIG_CFG0 = 32, WGRAD_BIG_NCFG = 4;  // wgrad cfgs 32-35: 32x32x16 large-tile kernels
-constexpr int WGRAD_LEAN_CFG0 = 36, WGRAD_LEAN_NCFG = 12;  // wgrad cfgs 36-47: lean-staging im2col (wgrad_lean.hip;
-                                                             // 44-47 on the 32x32x16 MFMA)
-int wgrad_lean_shape(int cfg, int& TN, int& TK);
-int wgrad_lean_ntiles(int cfg, const WgradArgs& a);
-int launch_wgrad_lean(const WgradArgs& a, int G, int cfg, hipStream_t st);
-int launch_wgrad_lean_batched(int cfg, const WgradJob* d_jobs, int nj, int64_t nblocks, dim3 grid, hipStream_t st);
-int wgrad_patch_shape(int cfg, int& TN, int& CB, int& W8, int& R);
-int wgrad_ntiles(int cfg, const WgradArgs& a);  // tiles per group of a wgrad launch, < 0: cfg invalid for a
+// weight-gradient configs: wgrad_tile.h; tiles per group of a wgrad launch, < 0: cfg invalid for a
+int wgrad_ntiles(int cfg, const WgradArgs& a);
 // cap > 0: at most cap hardware blocks walk the nblocks virtual blocks (persistent grid)
 int launch_wgrad_batched(int cfg, const WgradJob* d_jobs, int nj, int64_t nblocks, hipStream_t st, int64_t cap = 0);
 int launch_wgrad_finalize(const WgFinDesc* d_descs, int nd, int64_t nblocks, float scale, hipStream_t st);

@@ -1,4 +1,4 @@
-// Lean im2col weight gradient (configs WGRAD_LEAN_CFG0 .. + WGRAD_LEAN_NCFG - 1).
+// Lean im2col weight gradient (configs 36-47, wgrad_tile.h WGRAD_CONFIGS_LEAN).
 //
 // dW[n][k] = sum over output pixels m of dy[m][n] * X[m][k], X the im2col of the forward input (k = (kh*KW +
 // kw)*Cs + ci, the slab layout of every weight-gradient kernel: [G][splits][Npad][Kpad], summed by
@@ -16,7 +16,7 @@
 //     source segment, the LDS destination -- is fixed for the block and computed once, before the loop;
 //   * loads are branch-free: an out-of-image tap or a pixel past the split loads a valid dummy address and is
 //     zeroed by a select, so no exec-mask divergence splits the staging;
-//   * 32-bit offsets (every operand here is < 2^31 elements; checked on the host).
+//   * 32-bit offsets (every operand here is < 2^31 elements; checked on the host, conv.hip wgrad_ntiles).
 // Normalise-on-load inputs (the forward conv read act(BN(y))) are rebuilt on the way into LDS, as in wgrad_block.
 //
 // Configs 44-47 (BIG) are the same staging under wgrad_big_block's compute: 64 x 64 .. 128 x 128 tiles on the
@@ -24,37 +24,9 @@
 // form for batched launches of many jobs (Model C's Inception weight gradients: lean 16x16 tiles were 2x faster
 // per job alone but 45 % slower as batches, profiles/r6_wgrad_lean.md).  They split M like the large tiles
 // (engine/core.py wgrad_plan), not like the lean 16x16 configs.
-#include "kernels.h"
+#include "wgrad_tile.h"
 
 namespace mda {
-
-// (TN, TK, MCH pixels per chunk, 32x32x16 MFMA); keep in sync with ops/functional.py WGRAD_TILES (entries
-// WGRAD_LEAN_CFG0..)
-#define WGRAD_LEAN_CASES(X)                                                                                   \
-  case 36: X(16, 64, 256, false) case 37: X(16, 144, 128, false) case 38: X(32, 64, 256, false)               \
-  case 39: X(32, 144, 128, false) case 40: X(64, 64, 128, false) case 41: X(64, 128, 128, false)              \
-  case 42: X(128, 64, 128, false) case 43: X(128, 128, 64, false)                                             \
-  case 44: X(64, 64, 64, true) case 45: X(64, 128, 64, true) case 46: X(128, 64, 64, true)                    \
-  case 47: X(128, 128, 64, true)
-
-int wgrad_lean_shape(int cfg, int& TN, int& TK) {
-  static const int tn[] = {16, 16, 32, 32, 64, 64, 128, 128, 64, 64, 128, 128};
-  static const int tk[] = {64, 144, 64, 144, 64, 128, 64, 128, 64, 128, 64, 128};
-  if (cfg < WGRAD_LEAN_CFG0 || cfg >= WGRAD_LEAN_CFG0 + WGRAD_LEAN_NCFG) return -1;
-  TN = tn[cfg - WGRAD_LEAN_CFG0];
-  TK = tk[cfg - WGRAD_LEAN_CFG0];
-  return 0;
-}
-
-// im2col column group i (8 channels of one tap): channel offset within its source segment | kw << 14 | kh << 21
-// | segment << 28 | valid << 29 (0: the group lies past the reduction -- stages zeros)
-DEV int lean_encode(int i, int Ktot, int Cs8, int KW, int C0) {
-  if (i * 8 >= Ktot) return 0;
-  const int tap = i / Cs8, c = (i - tap * Cs8) * 8;
-  const int kh = tap / KW, kw = tap - kh * KW;
-  const int seg = c >= C0;
-  return (seg ? c - C0 : c) | (kw << 14) | (kh << 21) | (seg << 28) | (1 << 29);
-}
 
 constexpr int LEAN_BAD_ROW = -16384;  // first-tap row of a pixel past the split: every tap lands outside the image
 
@@ -77,6 +49,7 @@ DEV void wgrad_lean_block(const WgradArgs& a, const int tile, const int split, c
   __shared__ int s_ihw[2][MCH];  // ih0 << 16 | (iw0 & 0xffff)
   __shared__ int s_tab[KG];
   __shared__ __attribute__((aligned(16))) float s_nsc[TK], s_nsh[TK];
+  static_assert(MCH * LDX <= (1 << LEAN_DST_BITS) && MCH * LDY <= (1 << LEAN_DST_BITS), "xo / yo: LDS destination field");
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int ntk = (a.Kpad + TK - 1) / TK;
@@ -106,11 +79,11 @@ DEV void wgrad_lean_block(const WgradArgs& a, const int tile, const int split, c
     }
   };
 
-  if (tid < KG) s_tab[tid] = lean_encode(k0 / 8 + tid, Ktot, a.Cs >> 3, a.KW, a.src.C0);
+  if (tid < KG) s_tab[tid] = encode_kg(k0 / 8 + tid, Ktot, a.Cs >> 3, a.KW, a.src.C0);
   if (a.nol) {
     const float* kz = a.nol_consts + (int64_t)z * 4 * a.Cs;
     for (int t = tid; t < TK; t += 256) {
-      const int e = lean_encode(k0 / 8 + t / 8, Ktot, a.Cs >> 3, a.KW, a.src.C0);
+      const int e = encode_kg(k0 / 8 + t / 8, Ktot, a.Cs >> 3, a.KW, a.src.C0);
       const int c = (e & 16383) + ((e >> 28) & 1) * a.src.C0 + (t & 7);
       const bool ok = (e >> 29) & 1;
       s_nsc[t] = ok ? kz[c] : 0.f;
@@ -282,68 +255,13 @@ DEV void wgrad_lean_block(const WgradArgs& a, const int tile, const int split, c
 }
 
 template <int TN, int TK, int MCH, bool BIG>
-__global__ __launch_bounds__(256) void conv_wgrad_lean_kernel(WgradArgs a) {
-  wgrad_lean_block<TN, TK, MCH, BIG>(a, blockIdx.x, blockIdx.y, blockIdx.z);
+DEV void WgLean<TN, TK, MCH, BIG>::run(const WgradArgs& a, int tile, int split, int z) {
+  wgrad_lean_block<TN, TK, MCH, BIG>(a, tile, split, z);
 }
 
-template <int TN, int TK, int MCH, bool BIG>
-__global__ __launch_bounds__(256) void conv_wgrad_lean_batched_kernel(const WgradJob* __restrict__ jobs, int nj,
-                                                                       int64_t nvb) {
-  for (int64_t vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-    int lo = 0, hi = nj - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (jobs[mid].block0 <= vb) lo = mid; else hi = mid - 1;
-    }
-    const WgradJob& J = jobs[lo];
-    const int local = (int)(vb - J.block0);
-    const int per_z = J.ntiles * J.a.splits;
-    const int z = local / per_z, r = local - z * per_z;
-    wgrad_lean_block<TN, TK, MCH, BIG>(J.a, r % J.ntiles, r / J.ntiles, z);
-    __syncthreads();  // the next virtual block re-stages the LDS tables
-  }
-}
-
-// the host-side checks every lean launch needs: 32-bit staging offsets, fdiv24's exact range
-static bool lean_args_ok(const WgradArgs& a) {
-  const int64_t M = (int64_t)a.B * a.Ho * a.Wo;
-  const int64_t xin = (int64_t)a.B * a.Hi * a.Wi;
-  const int64_t ld = std::max(a.src.ld[0], a.src.C1 > 0 ? a.src.ld[1] : 0);
-  return M < (1 << 24) && xin * ld < ((int64_t)1 << 31) && M * a.ldd < ((int64_t)1 << 31) && a.Wi < 32768 &&
-         a.Hi < 16384 && a.KH < 128 && a.KW < 128;
-}
-
-int wgrad_lean_ntiles(int cfg, const WgradArgs& a) {
-  int TN, TK;
-  if (wgrad_lean_shape(cfg, TN, TK)) return -1;
-  if (!lean_args_ok(a)) return -2;
-  return ((a.Npad + TN - 1) / TN) * ((a.Kpad + TK - 1) / TK);
-}
-
-int launch_wgrad_lean(const WgradArgs& a, int G, int cfg, hipStream_t st) {
-  const int nt = wgrad_lean_ntiles(cfg, a);
-  if (nt < 0) return nt;
-#define LAUNCH_WGL(TN, TK, MCH, BIG)                                                                          \
-  hipLaunchKernelGGL((conv_wgrad_lean_kernel<TN, TK, MCH, BIG>), dim3(nt, a.splits, G), dim3(256), 0, st, a); \
-  break;
-  switch (cfg) {
-    WGRAD_LEAN_CASES(LAUNCH_WGL)
-    default: return -1;
-  }
-#undef LAUNCH_WGL
-  return (int)hipGetLastError();
-}
-
-int launch_wgrad_lean_batched(int cfg, const WgradJob* d_jobs, int nj, int64_t nblocks, dim3 grid, hipStream_t st) {
-#define LAUNCH_WGLB(TN, TK, MCH, BIG)                                                                               \
-  hipLaunchKernelGGL((conv_wgrad_lean_batched_kernel<TN, TK, MCH, BIG>), grid, dim3(256), 0, st, d_jobs, nj, nblocks); \
-  break;
-  switch (cfg) {
-    WGRAD_LEAN_CASES(LAUNCH_WGLB)
-    default: return -1;
-  }
-#undef LAUNCH_WGLB
-  return (int)hipGetLastError();
-}
+// the lean kernels (conv.hip launch_wgrad / launch_wgrad_batched start them)
+#define WGRAD_LEAN_KERNELS(ID, FAM, ...) WGRAD_KERNELS(, __VA_ARGS__)
+WGRAD_CONFIGS_LEAN(WGRAD_LEAN_KERNELS)
+#undef WGRAD_LEAN_KERNELS
 
 }  // namespace mda

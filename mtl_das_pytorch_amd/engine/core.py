@@ -23,12 +23,11 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..ops.functional import (WGRAD_BIG0, WGRAD_LEAN0, WGRAD_LEAN_N, WGRAD_PATCH, WGRAD_TILES, bnb_plan, patch_plan, patch_valid, wgrad_cfg,
-                              wgrad_ktiles)
+from ..ops.functional import (NREP, WGRAD_CONFIGS, bnb_plan, patch_plan, wgrad_cfg, wgrad_family, wgrad_ktiles,
+                              wgrad_ntiles)
 from ..ops.hip import lib, ptr
 from . import guard
 
-NREP = 32  # must match csrc/common.h
 # storage type of every activation gradient (data gradients, gradient sources, BN-tail side outputs and dz
 # buffers): bf16 as under autocast -- producers accumulate in fp32 and round once at the store, consumers sum
 # their sources in fp32 (csrc/common.h); half the bytes of the fp32 gradients every backward kernel moved
@@ -479,12 +478,12 @@ class ConvLayer:
         # largest split count any config can ask for)
         self.Kpad_w = pad_to(taps * self.Cs, 64)
         self._wgrad_args = None
-        max_splits = max(self.wgrad_plan(c)[0] for c in list(WGRAD_TILES) + list(WGRAD_PATCH) if self.wgrad_valid(c))
+        max_splits = max(self.wgrad_plan(c)[0] for c in WGRAD_CONFIGS if self.wgrad_valid(c))
         self.slab = arena.empty((self.G, max_splits, self.Npad, self.Kpad_w), torch.float32)
         self.set_wgrad_cfg(wgrad_cfg(self.Co, self.Kpad_w))
 
     # every split-M block reduces at least this many output pixels: with the weight gradients of all
-    # convs batched into one launch (csrc/conv.hip conv_wgrad_batched_kernel) the grid no longer has to
+    # convs batched into one launch (csrc/wgrad_tile.h wgrad_batched_kernel) the grid no longer has to
     # be filled by one conv's splits, and each extra split costs a full Npad x Kpad slab read in the
     # finalize (Model C: ~0.9 GB/step of slab traffic with grid-filling splits)
     # (512 / 2048 / 4096 measured within noise on A, C 7.10k at 1024 vs 6.83k at 2048)
@@ -500,22 +499,25 @@ class ConvLayer:
         """The K tiles of ``cfg`` cover this conv's padded reduction (exactly, except for the large-tile
         configs; patch configs: a 3x3 / s1 / p1 conv whose input channels split into whole CB slices and
         whose rows fit the tile width)."""
-        if cfg in WGRAD_PATCH:
-            return self.stem_geom is None and patch_valid(cfg, self.Cs, self.KH, self.KW, (self.sh, self.sw),
-                                                          (self.ph, self.pw), self.Hi, self.Wi, self.Ho, self.Wo,
-                                                          self.src_C0, self.src_C1)
-        return wgrad_ktiles(cfg, self.Kpad_w) > 0
+        if wgrad_family(cfg) == "patch" and self.stem_geom is not None:
+            return False
+        # the launch's arguments once the backward is emitted, before that the geometry with dense operands
+        return wgrad_ntiles(cfg, self._wgrad_args or {
+            "src": {"ld0": self.Cs, "C0": self.Cs, "C1": 0}, "ldd": self.Co, "B": self.B, "Hi": self.Hi, "Wi": self.Wi,
+            "Ho": self.Ho, "Wo": self.Wo, "Npad": self.Npad, "Cs": self.Cs, "KH": self.KH, "KW": self.KW,
+            "sh": self.sh, "sw": self.sw, "ph": self.ph, "pw": self.pw, "Kpad": self.Kpad_w}) >= 0
 
     def wgrad_plan(self, cfg: int):
-        if cfg in WGRAD_PATCH:
+        c = WGRAD_CONFIGS[cfg]
+        if c.family == "patch":
             # splits sized for ~128 blocks per job on Model A's layers (32 / 64 / 256 measured slower there);
             # the wide-row configs (128-pixel rows: Model C's 47x122 / 21x58 stem layers) fill the GPU with
             # ~512 blocks (tools/wgrad_cfg_sweep.py: 47x122 32->64 29 us at 512 blocks vs 53 us at 128)
-            wide = WGRAD_PATCH[cfg][2] >= 128
+            wide = c.W8 >= 128
             return patch_plan(cfg, self.B, self.Ho, self.Npad, self.Cs, self.G, 512 if wide else 128)
-        TN, TK, MCH = WGRAD_TILES[cfg]
+        TN, TK, MCH = c.TN, c.TK, c.MCH
         tiles = math.ceil(self.Npad / TN) * wgrad_ktiles(cfg, self.Kpad_w) * self.G
-        if WGRAD_LEAN0 <= cfg < WGRAD_LEAN0 + WGRAD_LEAN_N:
+        if c.family == "lean":
             # lean staging (csrc/wgrad_lean.hip) is bound by the load latency of its serial chunks: ~LEAN_BLOCKS
             # blocks per job, at least LEAN_MIN_CHUNKS chunks each, at most LEAN_MAX_SPLITS split slabs for the
             # finalize to sum (it runs on the step's tail)
@@ -525,7 +527,7 @@ class ConvLayer:
             return math.ceil(self.M_out / mps), mps
         # whole-reduction tiles (TK >= 128) have one tile per channel block: shorter per-block pixel
         # ranges keep enough blocks in flight (the finalize sums the extra splits with several lanes)
-        if cfg >= WGRAD_BIG0:
+        if c.family in ("big", "leanbig"):
             min_px = self.MIN_SPLIT_PX_BIG
         else:
             min_px = self.MIN_SPLIT_PX // 2 if TK >= 128 else self.MIN_SPLIT_PX

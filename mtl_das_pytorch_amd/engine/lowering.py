@@ -8,7 +8,7 @@ from typing import Callable, Dict, List, Optional
 
 import torch
 
-from ..ops.functional import LIVE_NSTATE, WGRAD_PATCH, WGRAD_TILES, gather_args, noise_args, selection_args, wgrad_ktiles
+from ..ops.functional import LIVE_NSTATE, WGRAD_CONFIGS, gather_args, noise_args, selection_args, wgrad_ktiles
 from ..ops.hip import lib
 from .core import (GRAD_DT, Act, BNLayer, ConvLayer, P, build_optseg_table, build_wgfin_table, optimizer_segments,
                    pad_to)
@@ -24,12 +24,11 @@ ACT_NONE, ACT_RELU, ACT_SIGMOID, SIGMUL, ADD_RELU, POOL_RELU = range(6)
 def _wgrad_cost(l: Launch) -> int:
     """MFMA work (MACs incl. tile padding) of one per-conv weight-gradient launch -- used to balance fan-out."""
     cfg, G, d = l.args
-    if cfg in WGRAD_PATCH:
-        TN, CB, _, R = WGRAD_PATCH[cfg]
-        px = d["splits"] * d["m_per_split"] * R * pad_to(d["Wo"], 8)
-        return px * G * math.ceil(d["Npad"] / TN) * TN * 9 * d["Cs"]
-    TN, TK, MCH = WGRAD_TILES[cfg]
-    return d["splits"] * d["m_per_split"] * G * TN * TK * math.ceil(d["Npad"] / TN) * wgrad_ktiles(cfg, d["Kpad"])
+    c = WGRAD_CONFIGS[cfg]
+    if c.family == "patch":
+        px = d["splits"] * d["m_per_split"] * c.R * pad_to(d["Wo"], 8)
+        return px * G * math.ceil(d["Npad"] / c.TN) * c.TN * 9 * d["Cs"]
+    return d["splits"] * d["m_per_split"] * G * c.TN * c.TK * math.ceil(d["Npad"] / c.TN) * wgrad_ktiles(cfg, d["Kpad"])
 
 
 _GRAD_KEYS = ("dgamma", "dbeta", "dgamma2", "dbeta2", "dW", "db")
@@ -828,7 +827,7 @@ class LoweredProgram:
     # the same cap for stream 0 only (its batches run serially after the data-gradient chain); None: as above
     WGRAD_MAX_BATCHES_S0 = None
     # hardware blocks of a side stream's batched weight-gradient launch (0: one per virtual block): a capped,
-    # persistent grid leaves CU slots free for the critical chain's kernels (csrc/conv.hip WGRAD_FOR_VBLOCKS)
+    # persistent grid leaves CU slots free for the critical chain's kernels (csrc/wgrad_tile.h wgrad_batched_kernel)
     SIDE_WGRAD_GRID = 0
 
     def merge_wgrad_cfgs(self, max_batches: Optional[int] = None) -> int:
@@ -914,7 +913,7 @@ class LoweredProgram:
 
     def batch_wgrads(self):
         """Replace the per-conv weight-gradient launches by batched launches, one per (stream, tile
-        config) (csrc/conv.hip conv_wgrad_batched_kernel).  Each stream's batch goes after that stream's
+        config) (csrc/wgrad_tile.h wgrad_batched_kernel).  Each stream's batch goes after that stream's
         last kernel -- after its join events, so nothing waits for the batch except the finalize, and e.g.
         Model A's level-branch weight gradients overlap the backbone's backward.  Called after the
         autotuner has fixed every conv's wgrad config and split count."""

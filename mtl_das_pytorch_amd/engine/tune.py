@@ -17,9 +17,8 @@ import torch
 
 from ..ops.functional import (CONV_DEEP_CFG0, CONV_DEEP_NCFG, CONV_GLDS_CFG0, CONV_GLDS_NCFG, CONV_LDS_CFG0,
                               CONV_LDS_NCFG, CONV_PATCH_CFG0, CONV_PATCH_NCFG, CONV_PATCHP_CFG0, CONV_PATCHP_NCFG,
-                              CONV_XCD, GDEEP_TILES, WGRAD_BIG0, WGRAD_LEAN0, WGRAD_LEAN_N, WGRAD_LEANBIG0, WGRAD_PATCH, WGRAD_TILES,
-                              conv_workspace,
-                              glds_cfg)
+                              CONV_XCD, GDEEP_TILES, WGRAD_PATCH, WGRAD_TILES, conv_workspace, glds_cfg, wgrad_big_cfg,
+                              wgrad_family, wgrad_lean_twin)
 from ..ops.hip import lib
 from .program import EventKeeper
 
@@ -240,11 +239,6 @@ def _wgrad_groups(prog) -> tuple:
     return wg, groups, weight
 
 
-def _big_cfg(conv) -> int:
-    """The large-tile weight-gradient config a conv's shape suits."""
-    return WGRAD_BIG0 + 2 * (conv.Npad > 64) + (conv.Kpad_w > 64)
-
-
 def tune_wgrad_batches(prog, cache: Dict[str, int], verbose: bool = False, passes: int = 1,
                        init_big: bool = False, init_lean=False) -> Dict[str, int]:
     """Choose the weight-gradient configs by the time of the BATCHED launches they end up in.
@@ -293,7 +287,7 @@ def tune_wgrad_batches(prog, cache: Dict[str, int], verbose: bool = False, passe
             if init_lean is not True and l0.stream not in init_lean:
                 continue
             cand = []
-            for c in range(WGRAD_LEAN0, WGRAD_LEAN0 + WGRAD_LEAN_N):
+            for c in [c for c in WGRAD_CFGS if wgrad_family(c) == "lean"]:
                 if not all(l.owner.wgrad_valid(c) for l in ls):
                     continue
                 l0.set_cfg(c)
@@ -303,8 +297,8 @@ def tune_wgrad_batches(prog, cache: Dict[str, int], verbose: bool = False, passe
                 assign[sig] = min(cand)[1]
     if init_big:
         for sig, ls in groups.items():
-            c = _big_cfg(ls[0].owner)
-            if assign[sig] not in WGRAD_PATCH and all(l.owner.wgrad_valid(c) for l in ls):
+            c = wgrad_big_cfg(ls[0].owner.Npad, ls[0].owner.Kpad_w)
+            if wgrad_family(assign[sig]) != "patch" and all(l.owner.wgrad_valid(c) for l in ls):
                 assign[sig] = c
     best = cost()
     for _ in range(passes):
@@ -359,9 +353,9 @@ def tune_wgrad_in_step(make_prog, X: torch.Tensor, labels: torch.Tensor, cache: 
                 res.append((_time(lambda c=c: L.wgrad(c, G, torch.cuda.current_stream().cuda_stream, d)), c))
         l.set_cfg(cfg0)
         res.sort()
-        big = _big_cfg(conv)
+        big = wgrad_big_cfg(conv.Npad, conv.Kpad_w)
         cands = [c for _, c in res[:topk]]
-        for c in (big, big - WGRAD_BIG0 + WGRAD_LEANBIG0):  # the large tile and its lean-staging form
+        for c in (big, wgrad_lean_twin(big)):  # the large tile and its lean-staging form
             if c in {c2 for _, c2 in res} and c not in cands:
                 cands.append(c)
         ranked[sig] = cands

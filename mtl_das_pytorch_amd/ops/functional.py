@@ -8,6 +8,7 @@ Every function requires a CUDA (ROCm) tensor and the built extension -- there is
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -15,7 +16,8 @@ import torch.nn.functional as F
 
 from .hip import lib, ptr, stream
 
-NREP = 32  # must match csrc/common.h
+# copies of csrc constants; tests/test_wgrad_configs.py compares every one with what the extension exports
+NREP = 32
 
 
 def _pad(x, m):
@@ -327,37 +329,61 @@ def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, in_hw: Tuple[int, int], stri
     return prepare_conv2d_dgrad(dy, w, in_hw, stride, padding, cin_stored, cfg, bn_stats, groups, add, out).run()
 
 
-WGRAD_TILES = {0: (16, 32, 128), 1: (32, 32, 128), 2: (32, 64, 64), 3: (64, 64, 64), 4: (16, 64, 128),
-               5: (16, 32, 256), 6: (32, 32, 256), 7: (64, 32, 64),
-               # whole-reduction tiles for small-Cout layers (csrc/conv.hip WGRAD_CFG_CASES)
-               8: (16, 192, 64), 9: (16, 128, 64), 10: (32, 192, 64), 11: (32, 320, 32),  # (TN, TK, MCH)
-               # large tiles on the 32x32x16 MFMA (csrc/conv.hip wgrad_big_block); their last K tile may be
-               # partial
-               32: (64, 64, 64), 33: (64, 128, 64), 34: (128, 64, 64), 35: (128, 128, 64),
-               # lean-staging im2col tiles (csrc/wgrad_lean.hip: per-chunk pixel table in LDS, per-thread staging
-               # constants, branch-free loads); partial last K tile
-               36: (16, 64, 256), 37: (16, 144, 128), 38: (32, 64, 256), 39: (32, 144, 128), 40: (64, 64, 128),
-               41: (64, 128, 128), 42: (128, 64, 128), 43: (128, 128, 64),
-               # the same staging under the large tiles' 32x32x16 MFMA compute and M split (cfg 32-35 + 12)
-               44: (64, 64, 64), 45: (64, 128, 64), 46: (128, 64, 64), 47: (128, 128, 64)}
-WGRAD_BIG0 = 32
-WGRAD_LEAN0, WGRAD_LEAN_N = 36, 8   # lean 16x16x32 configs (their own M split: engine/core.py wgrad_plan)
-WGRAD_LEANBIG0 = 44                 # lean large tiles 44-47: WGRAD_BIG0 + i -> WGRAD_LEANBIG0 + i
+# Weight-gradient tile configurations: the Python copy of csrc/wgrad_tile.h WGRAD_CONFIGS (the package imports and
+# lowers programs where the extension is absent; tests/test_wgrad_configs.py holds the two equal row by row).
+# im2col families: TN output channels x TK reduction columns, MCH pixels per LDS chunk; patch: TN x 9 taps x CB
+# input channels, W8 = max padded output width, R = output rows per strip.
+WgradCfg = namedtuple("WgradCfg", "family TN TK MCH CB W8 R", defaults=(0, 0, 0, 0, 0))
+WGRAD_FAMILIES = ("small", "whole", "patch", "big", "lean", "leanbig")  # csrc/wgrad_tile.h WgFamily, in its order
+
+
+def _cfgs(family, cfg0, fields, *rows):
+    return {cfg0 + i: WgradCfg(family, **dict(zip(fields, r))) for i, r in enumerate(rows)}
+
+
+_IM2COL, _PATCH = ("TN", "TK", "MCH"), ("TN", "CB", "W8", "R")
+WGRAD_CONFIGS = {
+    **_cfgs("small", 0, _IM2COL, (16, 32, 128), (32, 32, 128), (32, 64, 64), (64, 64, 64), (16, 64, 128),
+            (16, 32, 256), (32, 32, 256), (64, 32, 64)),
+    # whole-reduction tiles for small-Cout layers
+    **_cfgs("whole", 8, _IM2COL, (16, 192, 64), (16, 128, 64), (32, 192, 64), (32, 320, 32)),
+    # 3x3 / stride-1 patch kernels, padding 1 or 0 (csrc/conv.hip WgPatch::run)
+    **_cfgs("patch", 12, _PATCH, (16, 16, 88, 4), (32, 16, 88, 4), (32, 32, 48, 4), (64, 32, 24, 4),
+            (32, 32, 128, 2), (64, 32, 128, 2), (64, 16, 128, 2), (32, 16, 128, 2)),
+    # large tiles on the 32x32x16 MFMA (csrc/conv.hip wgrad_big_block); their last K tile may be partial
+    **_cfgs("big", 32, _IM2COL, (64, 64, 64), (64, 128, 64), (128, 64, 64), (128, 128, 64)),
+    # lean-staging im2col tiles (csrc/wgrad_lean.hip: per-chunk pixel table in LDS, per-thread staging constants,
+    # branch-free loads; their own M split: engine/core.py wgrad_plan); partial last K tile
+    **_cfgs("lean", 36, _IM2COL, (16, 64, 256), (16, 144, 128), (32, 64, 256), (32, 144, 128), (64, 64, 128),
+            (64, 128, 128), (128, 64, 128), (128, 128, 64)),
+    # the same staging under the large tiles' 32x32x16 MFMA compute and M split (wgrad_lean_twin)
+    **_cfgs("leanbig", 44, _IM2COL, (64, 64, 64), (64, 128, 64), (128, 64, 64), (128, 128, 64)),
+}
+WGRAD_TILES = {c: (v.TN, v.TK, v.MCH) for c, v in WGRAD_CONFIGS.items() if v.family != "patch"}
+WGRAD_PATCH = {c: (v.TN, v.CB, v.W8, v.R) for c, v in WGRAD_CONFIGS.items() if v.family == "patch"}
+
+
+def wgrad_family(cfg: int) -> str:
+    return WGRAD_CONFIGS[cfg].family
+
+
+def wgrad_big_cfg(Npad: int, Kpad: int) -> int:
+    """The large tile a conv's shape suits: 128 rows when Cout fills them, 128 columns when the reduction does."""
+    return 32 + 2 * (Npad > 64) + (Kpad > 64)
+
+
+def wgrad_lean_twin(cfg: int) -> int:
+    """The lean-staging form of a large-tile config (same tile, same M split); any other config is its own."""
+    return cfg + 12 if wgrad_family(cfg) == "big" else cfg
 
 
 def wgrad_ktiles(cfg: int, Kpad: int) -> int:
     """K tiles of an im2col weight-gradient config over a padded reduction of ``Kpad`` columns; 0 if the
     config cannot cover it (the small-tile kernels need TK | Kpad)."""
-    TK = WGRAD_TILES[cfg][1]
-    if cfg >= WGRAD_BIG0:
-        return math.ceil(Kpad / TK)
-    return 0 if Kpad % TK else Kpad // TK
-
-
-# 3x3 / stride-1 patch kernels, padding 1 or 0 (csrc/conv.hip wgrad_patch_block):
-# (TN, CB, max padded width, output rows per strip)
-WGRAD_PATCH = {12: (16, 16, 88, 4), 13: (32, 16, 88, 4), 14: (32, 32, 48, 4), 15: (64, 32, 24, 4),
-               16: (32, 32, 128, 2), 17: (64, 32, 128, 2), 18: (64, 16, 128, 2), 19: (32, 16, 128, 2)}
+    c = WGRAD_CONFIGS[cfg]
+    if c.family in ("small", "whole"):
+        return 0 if Kpad % c.TK else Kpad // c.TK
+    return math.ceil(Kpad / c.TK)
 
 
 def patch_valid(cfg, Cs, KH, KW, stride, padding, Hi, Wi, Ho, Wo, C0=None, C1=0) -> bool:
@@ -367,6 +393,35 @@ def patch_valid(cfg, Cs, KH, KW, stride, padding, Hi, Wi, Ho, Wo, C0=None, C1=0)
     return ((KH, KW) == (3, 3) and s == (1, 1) and p[0] in (0, 1) and p[1] in (0, 1)
             and (Ho, Wo) == (Hi + 2 * p[0] - 2, Wi + 2 * p[1] - 2) and Cs % CB == 0
             and _pad(Wo, 8) <= W8 and (R * _pad(Wo, 8)) % 32 == 0 and (C1 == 0 or C0 % CB == 0))
+
+
+KG_CH_BITS, KG_TAP_BITS = 14, 7  # csrc/conv_tile.h encode_kg: channel offset within a segment, tap index
+
+
+def wgrad_ntiles(cfg: int, d: dict) -> int:
+    """csrc/conv.hip wgrad_ntiles on the argument dict of a weight-gradient launch (geometry and pitches only):
+    tiles per group, -1 no such config, -2 the config cannot take this conv -- its tiles do not cover it, or a
+    value its kernel packs into a bit field or a 32-bit offset would not fit."""
+    c = WGRAD_CONFIGS.get(cfg)
+    if c is None:
+        return -1
+    src, Cs, Kpad, KH, KW = d["src"], d["Cs"], d["Kpad"], d["KH"], d["KW"]
+    C0, C1 = src.get("C0", 0), src.get("C1", 0)
+    rows = math.ceil(d["Npad"] / c.TN)
+    if c.family == "patch":
+        ok = patch_valid(cfg, Cs, KH, KW, (d["sh"], d["sw"]), (d["ph"], d["pw"]), d["Hi"], d["Wi"], d["Ho"], d["Wo"],
+                         C0, C1) and Kpad >= 9 * Cs
+        return rows * (Cs // c.CB) if ok else -2
+    w0 = min(C0, Cs)  # encode_kg: offsets below w0 in segment 0, below Cs - w0 in segment 1; taps below KH, KW
+    if max(w0, Cs - w0) - 8 >= 1 << KG_CH_BITS or max(KH, KW) - 1 >= 1 << KG_TAP_BITS:
+        return -2
+    if c.family in ("lean", "leanbig"):
+        M, xin = d["B"] * d["Ho"] * d["Wo"], d["B"] * d["Hi"] * d["Wi"]
+        ld = max(src["ld0"], src.get("ld1", src["ld0"]) if C1 > 0 else 0)
+        if not (M < 1 << 24 and xin * ld < 1 << 31 and M * d["ldd"] < 1 << 31 and d["Wi"] < 32768 and d["Hi"] < 16384
+                and KH < 128 and KW < 128 and rows * c.TN - 8 < 1 << KG_CH_BITS):
+            return -2
+    return rows * wgrad_ktiles(cfg, Kpad) or -2
 
 
 def patch_plan(cfg, B, Ho, Npad, Cs, G=1, target=512):
@@ -399,28 +454,26 @@ def prepare_conv2d_wgrad(x, dy, w_shape, stride=1, padding=0, x2=None, splits=No
     Npad = _pad(Co, 16)
     if cfg is None:
         cfg = wgrad_cfg(Co, Kpad)
-    if cfg in WGRAD_PATCH:
-        if not patch_valid(cfg, Cs, KH, KW, (sh, sw), (ph, pw), H, W, Ho, Wo, x.shape[-1], C1):
-            raise ValueError(f"wgrad patch config {cfg} does not fit this convolution")
+    src = {"p0": ptr(x), "ld0": x.shape[-1], "C0": x.shape[-1], "C1": C1}
+    if x2 is not None:
+        src.update({"p1": ptr(x2), "ld1": C1})
+    d = {"src": src, "dy": ptr(dy), "ldd": Co, "B": B, "Hi": H, "Wi": W, "Ho": Ho, "Wo": Wo, "Co": Co, "Npad": Npad,
+         "Cs": Cs, "KH": KH, "KW": KW, "sh": sh, "sw": sw, "ph": ph, "pw": pw, "Kpad": Kpad}
+    tiles = wgrad_ntiles(cfg, d)
+    if tiles < 0:
+        raise ValueError(f"wgrad config {cfg} {WGRAD_CONFIGS.get(cfg)} does not fit this convolution (Kpad {Kpad})")
+    if wgrad_family(cfg) == "patch":
         splits, mps = patch_plan(cfg, B, Ho, Npad, Cs)
     else:
-        TN, TK, MCH = WGRAD_TILES[cfg]
-        if not wgrad_ktiles(cfg, Kpad):
-            raise ValueError(f"wgrad config {cfg} (TK={TK}) does not tile the padded reduction {Kpad}")
+        MCH = WGRAD_CONFIGS[cfg].MCH
         M = B * Ho * Wo
-        tiles = math.ceil(Npad / TN) * wgrad_ktiles(cfg, Kpad)
         if splits is None:
             splits = max(1, min(math.ceil(M / MCH), math.ceil(512 / tiles)))
         mps = _pad(math.ceil(M / splits), MCH)
         splits = math.ceil(M / mps)
     from ..engine import guard
     slab = guard.alloc((1, splits, Npad, Kpad), torch.float32, x.device, label=f"wgrad slab cfg {cfg}")
-    src = {"p0": ptr(x), "ld0": x.shape[-1], "C0": x.shape[-1], "C1": C1}
-    if x2 is not None:
-        src.update({"p1": ptr(x2), "ld1": C1})
-    d = {"src": src, "dy": ptr(dy), "ldd": Co, "slab": ptr(slab), "splits": splits, "m_per_split": mps,
-         "B": B, "Hi": H, "Wi": W, "Ho": Ho, "Wo": Wo, "Co": Co, "Npad": Npad, "Cs": Cs, "KH": KH, "KW": KW,
-         "sh": sh, "sw": sw, "ph": ph, "pw": pw, "Kpad": Kpad}
+    d.update(slab=ptr(slab), splits=splits, m_per_split=mps)
 
     if nol is not None:  # (consts [1, 4, Cs] fp32: scale, shift, mean, invstd; kind)
         d["nol"] = {"consts": ptr(nol[0]), "kind": nol[1]}
@@ -1177,7 +1230,7 @@ def live_map(table: torch.Tensor, fs, F: int, Wf: int, cf: int, jcap: int, jlo, 
 
 
 # ---- raw-rate recordings: FIR and decimation ahead of the ring (csrc/resample.hip) ------------------------------
-DECIMATE_TILE = 128  # outputs of one block; must match csrc/kernels.h
+DECIMATE_TILE = 128  # outputs of one block (csrc/kernels.h)
 
 
 def decimate_carry(rows: int, L: int, device) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -5,7 +5,7 @@ end.  The bindings are called directly with descriptors from the project's own b
 optimizer_segments, build_optseg_table, finalize_lanes, ConvLayer.wgrad_plan, stem_pack_geom), so the host tables
 are under test too.
 
-A. Weight-gradient kernels (csrc/conv.hip wgrad_block / wgrad_big_block / wgrad_patch_block, csrc/wgrad_lean.hip),
+A. Weight-gradient kernels (csrc/conv.hip wgrad_block / wgrad_big_block / WgPatch::run, csrc/wgrad_lean.hip),
    per-conv and batched (capped persistent grid), in the forms the engine launches: groups with their own strides,
    pitched inputs and dy, two segments, normalise-on-load constants per group, the engine's split plan and two
    forced ones (a last split shorter than a chunk; one split), every geometry family, Co off the tile, partial K

@@ -23,12 +23,7 @@ from mtl_das_pytorch_amd.data.synthetic import generate  # noqa: E402
 from mtl_das_pytorch_amd.engine.core import ConvLayer  # noqa: E402
 from mtl_das_pytorch_amd.engine.tune import _time, autotune_program, step_time_us  # noqa: E402
 from mtl_das_pytorch_amd.models import build_model, encode_joint  # noqa: E402
-from mtl_das_pytorch_amd.ops.functional import WGRAD_BIG0, WGRAD_PATCH  # noqa: E402
-
-
-def big_cfg(conv) -> int:
-    """Large tile for a conv: 128 rows when Cout fills them, 128 columns when the reduction does."""
-    return WGRAD_BIG0 + 2 * (conv.Npad > 64) + (conv.Kpad_w > 64)
+from mtl_das_pytorch_amd.ops.functional import wgrad_big_cfg, wgrad_family  # noqa: E402
 
 
 def build(model_type: str, policy: str):
@@ -46,9 +41,9 @@ def build(model_type: str, policy: str):
         for l in p.bwd.launches:
             if l.name != "conv_wgrad":
                 continue
-            if policy == "big" and l.args[0] in WGRAD_PATCH:
+            if policy == "big" and wgrad_family(l.args[0]) == "patch":
                 continue
-            c = big_cfg(l.owner)
+            c = wgrad_big_cfg(l.owner.Npad, l.owner.Kpad_w)
             if l.owner.wgrad_valid(c):
                 l.set_cfg(c)
     p.merge_wgrad_cfgs()

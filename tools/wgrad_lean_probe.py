@@ -14,10 +14,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mtl_das_pytorch_amd.data.synthetic import generate  # noqa: E402
 from mtl_das_pytorch_amd.engine.tune import _time, autotune_program  # noqa: E402
 from mtl_das_pytorch_amd.models import build_model, encode_joint  # noqa: E402
-from mtl_das_pytorch_amd.ops.functional import WGRAD_BIG0, WGRAD_LEAN0, WGRAD_LEAN_N, WGRAD_LEANBIG0  # noqa: E402
+from mtl_das_pytorch_amd.ops.functional import WGRAD_CONFIGS, wgrad_lean_twin  # noqa: E402
 from mtl_das_pytorch_amd.ops.hip import lib  # noqa: E402
 
-LEAN = list(range(WGRAD_LEAN0, WGRAD_LEAN0 + WGRAD_LEAN_N)) + list(range(WGRAD_LEANBIG0, WGRAD_LEANBIG0 + 4))
+LEAN = [c for c, v in WGRAD_CONFIGS.items() if v.family in ("lean", "leanbig")]
 
 
 def main():
@@ -68,7 +68,7 @@ def main():
     # batched launches per stream: shipped configs vs every job on its best lean config (one batch per config)
     # the shipped table with every large-tile job (32-35) on its lean-staging twin (44-47): same tiles and M split,
     # only the staging differs -- the throughput comparison of the two staging forms
-    twin = {k: (c - WGRAD_BIG0 + WGRAD_LEANBIG0 if WGRAD_BIG0 <= c < WGRAD_BIG0 + 4 else c) for k, c in shipped.items()}
+    twin = {k: wgrad_lean_twin(c) for k, c in shipped.items()}
     for label, pick in (("shipped", shipped), ("lean", best), ("leanbig-twins", twin)):
         tot = 0.0
         for l in wg:
