@@ -10,6 +10,8 @@
         # run: the floor is the running median of the last 64 time indices (or --noise_floor P, a fixed power)
     python infer.py ... --decimate 10 [--taps taps.npy] [--chunk 20000]   # the recording is at the raw rate (fp32 or
         # int16): low-pass FIR and decimation by 10 first; --chunk then counts raw samples
+    python infer.py ... --common_mode median [--chunk 2000]   # subtract the per-sample median (or mean) over the fiber
+        # from the stream the windows are cut from (after --decimate): laser and interrogator noise common to all
 """
 import argparse
 import os
@@ -53,6 +55,9 @@ def main():
     ap.add_argument("--taps", default=None,
                     help="with --decimate: the FIR's taps, a .npy vector of at most 1025 (default: a Kaiser-windowed "
                          "sinc of 16 * D + 1 taps with its cut-off at 0.375 / D)")
+    ap.add_argument("--common_mode", choices=["median", "mean"], default=None,
+                    help="subtract the common mode -- per time sample the lower median or the mean over the fiber "
+                         "-- from the stream the windows are cut from (with --decimate: after it); default: off")
     args = ap.parse_args()
     taps = None
     if args.taps is not None and args.decimate is None:
@@ -128,7 +133,7 @@ def main():
                 rec = rec.astype(np.float32)
         res = predict_recording(model, args.model, torch.from_numpy(rec), stride=stride, batch=args.batch_size,
                                 ctx=ctx, use_engine=use_engine, gate_db=args.gate_db, noise_floor=noise_floor,
-                                decimate=args.decimate, taps=taps)
+                                decimate=args.decimate, taps=taps, common_mode=args.common_mode)
     if ctx.is_main:
         import pandas as pd
         cols = {"fiber_start": res["positions"][:, 0], "time_start": res["positions"][:, 1]}
@@ -157,6 +162,8 @@ def main():
             if args.decimate is not None:
                 extra = {"time_edges_raw": np.minimum(np.arange(ntc + 1) * cell[1], shape[1]) * args.decimate,
                          "decimate": args.decimate, "taps": taps}
+            if args.common_mode is not None:
+                extra["common_mode"] = args.common_mode
             np.savez(args.map, fiber_edges=np.minimum(np.arange(nfc + 1) * cell[0], shape[0]),
                      time_edges=np.minimum(np.arange(ntc + 1) * cell[1], shape[1]), **extra, **maps)
             print(f"{nfc} x {ntc} cells -> {args.map}")
@@ -167,7 +174,8 @@ def live_run(model, args, rec, stride, cell, ctx, use_engine, noise_floor="runni
     """The recording through a LiveRecording, ``--chunk`` time samples at a time: the result dict of
     predict_recording (windows in its order) and, with ``cell``, the maps of prediction_map.  With ``--gate_db`` the
     live gate at ``noise_floor`` ("running" or a power).  With ``--decimate`` the chunks are raw (an int16 recording
-    is pushed as int16) and the ring counts decimated samples."""
+    is pushed as int16) and the ring counts decimated samples.  With ``--common_mode`` the common mode is removed
+    from every chunk on its way into the ring."""
     import numpy as np
     from mtl_das_pytorch_amd.inference import WINDOW, LiveRecording
     rec3 = rec if rec.ndim == 3 else rec[None]
@@ -178,7 +186,7 @@ def live_run(model, args, rec, stride, cell, ctx, use_engine, noise_floor="runni
                          ctx=ctx, use_engine=use_engine, gate_db=args.gate_db,
                          noise_floor=noise_floor if args.gate_db is not None else "running",
                          floor_history=args.floor_history, floor_warmup=args.floor_warmup or 1,
-                         decimate=args.decimate, taps=taps)
+                         decimate=args.decimate, taps=taps, common_mode=args.common_mode)
     dtype = np.int16 if (args.decimate is not None and rec3.dtype == np.int16) else np.float32
     outs = []
     for t in range(0, T, args.chunk):

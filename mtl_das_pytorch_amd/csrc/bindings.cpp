@@ -542,6 +542,16 @@ void fir_decimate(int64_t stream, py::dict d) {
   check(rc, "fir_decimate");
 }
 
+// a refused common_mode is the caller's argument error: ValueError
+void common_mode(int64_t stream, py::dict d) {
+  CommonModeArgs a{};
+  a.x = P<const float>(d, "x"); a.out = P<float>(d, "out"); a.trace = P<float>(d, "trace");
+  a.rows = I(d, "rows"); a.F = I(d, "F"); a.n = I(d, "n"); a.pitch = I(d, "pitch"); a.out_pitch = I(d, "out_pitch");
+  const int rc = launch_common_mode(a, (int)I(d, "how"), S(stream));
+  if (rc == -2) throw py::value_error("common_mode: arguments refused (rc=-2)");
+  check(rc, "common_mode");
+}
+
 void pool3(int is_max, int backward, int64_t stream, py::dict d) {
   PoolArgs a{};
   a.x = P<const bf16_t>(d, "x"); a.ldx = (int)I(d, "ldx");
@@ -685,6 +695,9 @@ PYBIND11_MODULE(_mda_hip, m) {
   m.attr("DECIMATE_TILE") = DECIMATE_TILE;
   m.attr("DECIMATE_MAX_FACTOR") = DECIMATE_MAX_FACTOR;
   m.attr("DECIMATE_MAX_TAPS") = DECIMATE_MAX_TAPS;
+  m.def("common_mode", &common_mode);
+  m.attr("COMMON_MODE_TILE") = COMMON_MODE_TILE;
+  m.attr("COMMON_MODE_MAX_F") = COMMON_MODE_MAX_F;
   m.def("wgrad_table", &wgrad_table);
   m.def("wgrad_configs", &wgrad_configs);
   m.def("wgrad_ntiles", &wgrad_ntiles_of);

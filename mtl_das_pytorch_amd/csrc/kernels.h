@@ -496,6 +496,24 @@ int64_t fir_output_count(int64_t carry_len, int64_t skip, int64_t n, int L, int 
 // -2 unless 1 <= D <= 64, 1 <= L <= 1025, 0 <= carry_len <= L - 1, skip >= 0, m = fir_output_count(..), every
 // pointer the launch uses is non-null and carry_out is not carry_in
 int launch_fir_decimate(const FirArgs& a, int itype, hipStream_t st);
+// common_mode.hip: the common mode -- per channel and time sample one value over the fiber, the lower median or the
+// mean -- subtracted from every fiber position (data/common_mode.py is the definition).  Columns are independent.
+constexpr int COMMON_MODE_TILE = 32;      // consecutive time columns of one block
+constexpr int COMMON_MODE_THREADS = 256;  // COMMON_MODE_TILE columns x 8 row groups
+// 1 <= F: the selection's counters are 32-bit and would hold more; one block walks all F rows of its columns four
+// times, and beyond this length a selection split along the fiber is the kernel to write
+constexpr int COMMON_MODE_MAX_F = 1 << 20;
+enum { COMMON_MODE_MEDIAN = 0, COMMON_MODE_MEAN = 1 };
+struct CommonModeArgs {
+  const float* x;  // [rows][F][pitch], n live columns
+  float* out;      // [rows][F][out_pitch]; x itself (then out_pitch = pitch) or apart from it
+  float* trace;    // [rows][n]: the value subtracted; may be null
+  int64_t rows, F, n, pitch, out_pitch;
+};
+// -2 unless how is one of the two, rows >= 1, 1 <= F <= COMMON_MODE_MAX_F, 0 <= n < 2^31, n <= both pitches < 2^31,
+// rows F < 2^32, the grid is below 2^31 blocks, x and out are non-null, out is x with x's pitch or does not overlap it, and trace overlaps
+// neither; n = 0 launches nothing
+int launch_common_mode(const CommonModeArgs& a, int how, hipStream_t st);
 // synth.hip: on-device synthetic DAS samples (data/synthetic.py physical model, Philox noise)
 constexpr int SYNTH_NPARAM = 9;  // per sample: distance, event, x0, t0, jitter[4], snr_db
 struct SynthArgs {

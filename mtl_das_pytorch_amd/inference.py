@@ -28,6 +28,12 @@ A recording at the interrogator's raw rate (``decimate=D``, fp32 or int16) is lo
 (data/resample.py is the definition; csrc/resample.hip on the engine path): :func:`decimate_recording` for a whole
 recording, and in :class:`LiveRecording` piece by piece with the filter's state carried across the pushes, so the
 decimated stream does not depend on how the raw one was cut.
+
+``common_mode="median" | "mean"`` subtracts, per time sample, the lower median or the mean over the fiber from the
+stream the windows are cut from -- the common mode, which would otherwise open the gate on the whole fiber
+(data/common_mode.py is the definition; csrc/common_mode.hip on the engine path): :func:`remove_common_mode` for a
+whole recording, and in :class:`LiveRecording` on every chunk before it enters the ring.  Time columns are
+independent, so no state is carried and the cut of a stream does not matter.
 """
 from __future__ import annotations
 
@@ -224,11 +230,58 @@ def decimate_recording(rec, D: int, taps=None, device=None, use_engine: Optional
     return torch.from_numpy(fir_decimate_reference(raw.cpu().numpy(), h, D).astype(np.float32)).to(device)
 
 
+def _model_rate_recording(rec) -> torch.Tensor:
+    """A recording or chunk at the model's rate as an fp32 tensor [C, F, T]; int16 is the raw rate's type and is
+    refused."""
+    x = torch.as_tensor(rec)
+    if x.dtype == torch.int16:
+        raise ValueError("an int16 recording is at the raw rate: it needs decimate")
+    if x.dim() == 2:
+        x = x.unsqueeze(0)
+    if x.dim() != 3:
+        raise ValueError(f"a recording is [F, T] or [C, F, T], got {tuple(x.shape)}")
+    return x.float()
+
+
+def _remove_common_mode(x: torch.Tensor, how: str, device, use_engine: bool, own: bool):
+    """:func:`remove_common_mode` of the fp32 [C, F, T] tensor ``x``; ``own``: ``x`` is a copy of the caller's data
+    that may be overwritten."""
+    if use_engine:
+        from .ops import functional as HF
+        x_d = x.to(device).contiguous()
+        own = own or x_d.data_ptr() != x.data_ptr()  # the upload or the repacking made a copy
+        return HF.common_mode(x_d, how, out=x_d if own else None)
+    from .data.common_mode import common_mode_reference
+    y, m = common_mode_reference(x.detach().cpu().numpy(), how)
+    return torch.from_numpy(y).to(device), torch.from_numpy(m).to(device)
+
+
+@torch.no_grad()
+def remove_common_mode(rec, how: str = "median", device=None, use_engine: Optional[bool] = None):
+    """The recording ``rec`` ([F, T] or [C, F, T], at the model's rate) minus its common mode: per channel and time
+    sample the lower median (``how="median"``) or the mean (``"mean"``) over the fiber (data/common_mode.py is the
+    definition).  Returns ``(clean [C, F, T] fp32, trace [C, T] fp32)``, ``trace`` the value subtracted.  On the
+    engine path the recording is uploaded, one ``common_mode`` launch runs on it and the result stays on the device,
+    with the definition's bits; elsewhere the reference.  A device tensor passed in is never modified (a copy this
+    function made itself is cleaned in place).  The estimate is over the whole fiber; a sub-range is not offered."""
+    from .data.common_mode import as_common_mode
+    how = as_common_mode(how)
+    if how is None:
+        raise ValueError("remove_common_mode needs 'median' or 'mean'")
+    raw = torch.as_tensor(rec)
+    x = _model_rate_recording(raw)
+    device = torch.device(device) if device is not None else x.device
+    if use_engine is None:
+        use_engine = device.type == "cuda"
+    return _remove_common_mode(x, how, device, use_engine, own=x.data_ptr() != raw.data_ptr())
+
+
 @torch.no_grad()
 def predict_recording(model: nn.Module, model_type: str, rec: torch.Tensor, stride=(100, 125), batch: int = 32,
                       ctx: Optional[DistContext] = None, device=None, use_engine: Optional[bool] = None,
                       windows: Optional[str] = None, runner=None, gate_db: Optional[float] = None,
-                      noise_floor="auto", decimate: Optional[int] = None, taps=None) -> Dict:
+                      noise_floor="auto", decimate: Optional[int] = None, taps=None,
+                      common_mode: Optional[str] = None) -> Dict:
     """Per-window predictions for one recording.  Returns numpy arrays: ``positions`` [N, 2], and per task
     (``distance`` / ``event`` as the model provides) ``<task>_pred`` [N] and ``<task>_prob`` [N, k].
 
@@ -250,15 +303,28 @@ def predict_recording(model: nn.Module, model_type: str, rec: torch.Tensor, stri
     ``taps`` first; everything else runs on the result as it does without, every rank decimating for itself.  The
     result gains ``raw_time_start`` = ``positions[:, 1] * D`` and ``raw_time_stop`` =
     ``(positions[:, 1] + Wt - 1) * D + L``, one past the last raw sample the window depends on.  None: ``rec`` is at
-    the model's rate."""
+    the model's rate.
+
+    ``common_mode`` = ``"median"`` or ``"mean"``: :func:`remove_common_mode` is applied to the stream the windows
+    are cut from -- with ``decimate`` that is the decimated recording, after the FIR: fp32, and D times fewer columns
+    -- and gate, selection, windows and maps run unchanged on the result, every rank cleaning for itself as it
+    decimates for itself.  The mean commutes with the FIR (both are linear, up to rounding); the median does not:
+    the median of the decimated recording is what is removed, not the decimated median of the raw one.  An int16
+    recording without ``decimate`` is an error.  None: nothing is removed."""
     device = torch.device(device) if device is not None else (ctx.device if ctx else torch.device("cpu"))
     if use_engine is None:
         use_engine = device.type == "cuda"
     D, h = _decimation(decimate, taps)
-    if D is not None:
-        res = predict_recording(model, model_type, decimate_recording(rec, D, h, device, use_engine), stride, batch,
-                                ctx, device, use_engine, windows, runner, gate_db, noise_floor)
-        return _raw_times(res, D, len(h))
+    from .data.common_mode import as_common_mode
+    how = as_common_mode(common_mode)
+    if D is not None or how is not None:
+        own = D is not None  # the decimated recording is this call's own
+        front = decimate_recording(rec, D, h, device, use_engine) if own else _model_rate_recording(rec)
+        if how is not None:
+            front = _remove_common_mode(front, how, device, use_engine, own)[0]
+        res = predict_recording(model, model_type, front, stride, batch, ctx, device, use_engine, windows, runner,
+                                gate_db, noise_floor)
+        return _raw_times(res, D, len(h)) if D is not None else res
     if windows is None:
         windows = "resident" if use_engine else "materialize"
     if windows not in ("resident", "materialize"):
@@ -731,10 +797,19 @@ class _TorchLive:
         self.recent = np.zeros((0, len(fs)))  # fp64 powers of the last history - 1 time indices
         self.total = 0
 
+    common_mode = None  # "median" / "mean": removed from every chunk before it enters the ring
+
+    def set_common_mode(self, how: str):
+        self.common_mode = how
+
     def append(self, chunk: torch.Tensor):
         n = chunk.shape[2]
         cols = (self.total + torch.arange(n)) % self.R
-        self.ring[:, :, cols] = chunk.detach().to("cpu", torch.float32)
+        chunk = chunk.detach().to("cpu", torch.float32)
+        if self.common_mode is not None:
+            from .data.common_mode import common_mode_reference
+            chunk = torch.from_numpy(common_mode_reference(chunk.numpy(), self.common_mode)[0])
+        self.ring[:, :, cols] = chunk
         self.total += n
 
     def flush(self):
@@ -861,7 +936,22 @@ class _EngineLive:
             dst.copy_(src, non_blocking=True)
             self.staged = torch.cuda.Event()
             self.staged.record()
+        self._clean(dst)
         self.HF.ring_append(self.ring, self.state, dst, len(self.fs), self.st, self.window[1])
+
+    common_mode = None  # "median" / "mean": removed from every staged chunk before it enters the ring
+
+    def set_common_mode(self, how: str):
+        """The common-mode stage: one eager launch, in place, on the staged chunk ahead of each ``ring_append`` --
+        outside the captured graph, and nothing is read back.  ``cm_trace`` takes the values subtracted (the
+        launch's own buffer; the live path does not return them)."""
+        self.common_mode = how
+        self.cm_trace = torch.empty(self.ring.shape[0] * (self.R - self.window[1]), device=self.ring.device)
+
+    def _clean(self, dst: torch.Tensor):
+        if self.common_mode is not None:
+            C, _, n = dst.shape
+            self.HF.common_mode(dst, self.common_mode, out=dst, trace=self.cm_trace[:C * n].view(C, n))
 
     def flush(self):
         self.HF.ring_append(self.ring, self.state, None, len(self.fs), self.st, self.window[1], flush=True)
@@ -899,6 +989,7 @@ class _EngineLive:
                              carry_out=self.carry[1 - self.cur])
         self.cur = 1 - self.cur
         if m:
+            self._clean(dst)
             self.HF.ring_append(self.ring, self.state, dst, len(self.fs), self.st, self.window[1])
 
     def evaluate(self, starts):
@@ -987,7 +1078,15 @@ class LiveRecording:
     (csrc/resample.hip; ``DecimatorBook`` mirrors the counts on the host), so the decimated stream -- and with it
     every result -- has the same bits however the raw stream is cut.  A push that completes no output returns an
     empty result; ``flush()`` drops the carried raw samples.  The results gain ``raw_time_start`` /
-    ``raw_time_stop`` as :func:`predict_recording`'s.  None: chunks are at the model's rate."""
+    ``raw_time_stop`` as :func:`predict_recording`'s.  None: chunks are at the model's rate.
+
+    ``common_mode`` = ``"median"`` or ``"mean"``: the common mode (:func:`remove_common_mode`) is removed from every
+    piece before it enters the ring -- with ``decimate`` from the decimated piece, as :func:`predict_recording`
+    does.  Time columns are independent, so nothing is carried and the calls together equal
+    ``predict_recording(rec, common_mode=...)`` on the concatenated chunks.  On the engine backend it is one eager
+    launch, in place, on the staged chunk ahead of each append (csrc/common_mode.hip): outside the captured graph
+    (``captures`` stays at 1), nothing read back, and a device chunk passed in is not modified.  The values
+    subtracted are not returned by the live path.  None: nothing is removed."""
 
     RAW_PIECE = 1 << 24  # raw elements staged per piece at most (and never below one decimation's D per row)
 
@@ -995,10 +1094,13 @@ class LiveRecording:
                  ring: int = 8 * WINDOW[1], batch: int = 32, device=None, use_engine: Optional[bool] = None,
                  ctx: Optional[DistContext] = None, table_indices: Optional[int] = None, window=WINDOW,
                  gate_db: Optional[float] = None, noise_floor="running", floor_history: int = 64,
-                 floor_warmup: int = 8, decimate: Optional[int] = None, taps=None):
+                 floor_warmup: int = 8, decimate: Optional[int] = None, taps=None,
+                 common_mode: Optional[str] = None):
         if ctx is not None and ctx.enabled and ctx.world > 1:
             raise ValueError("a live recording is not sharded: world > 1 is not supported")
         self.decimate, self.taps = _decimation(decimate, taps)
+        from .data.common_mode import as_common_mode
+        self.common_mode = as_common_mode(common_mode)
         self.gate = None
         if gate_db is not None:
             self.gate = _live_gate(gate_db, noise_floor, floor_history, floor_warmup)
@@ -1023,6 +1125,8 @@ class LiveRecording:
         self.backend = backend(model, model_type, self.C, self.F, int(ring), self.fs, self.window, self.stride[1],
                                self.book.jcap, K, batch, device, **({} if self.gate is None else {"gate": self.gate}))
         self.backend.cf = self.cell[0] if self.cell is not None else None
+        if self.common_mode is not None:
+            self.backend.set_common_mode(self.common_mode)
         if self.decimate is not None:
             from .data.resample import DecimatorBook
             self.dbook = DecimatorBook(len(self.taps), self.decimate)

@@ -1301,3 +1301,70 @@ def fir_decimate(raw: torch.Tensor, carry_in: Optional[torch.Tensor], carry_len:
                                   "rows": rows, "n": n, "pitch": pitch, "m": m, "carry_len": carry_len, "skip": skip,
                                   "D": D, "L": L, "itype": 1 if raw.dtype == torch.int16 else 0})
     return out, carry_out
+
+
+# ---- common-mode removal ahead of the windows (csrc/common_mode.hip) -------------------------------------------
+def _time_rows(t: torch.Tensor, name: str) -> int:
+    """The row pitch of ``t`` [C, F, n] as the kernels read it: fp32 on the device, contiguous along time with one
+    pitch over all C * F rows (a slice along time of a contiguous tensor will do)."""
+    if t.dim() != 3:
+        raise ValueError(f"{name} must be [C, F, n], got {tuple(t.shape)}")
+    if not t.is_cuda:
+        raise RuntimeError("HIP ops need a GPU tensor")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32, got {t.dtype}")
+    C, Fn, n = t.shape
+    if n == 0:
+        return 0
+    pitch = t.stride(1) if Fn > 1 else (t.stride(0) // Fn if C > 1 else n)
+    if t.stride(2) != 1 or pitch < n or (C > 1 and t.stride(0) != Fn * pitch):
+        raise ValueError(f"{name} must be contiguous along time with one row pitch")
+    return pitch
+
+
+def _span(t: torch.Tensor, count: int) -> Tuple[int, int]:
+    return t.data_ptr(), t.data_ptr() + 4 * count
+
+
+def common_mode(x: torch.Tensor, how: str, out: Optional[torch.Tensor] = None,
+                trace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``x`` [C, F, n] fp32 minus its common mode, the per-sample lower median (``how = "median"``) or mean
+    (``"mean"``) over the fiber (data/common_mode.py ``common_mode_reference`` is the definition; the device gives
+    its bits).  ``x`` and ``out`` are contiguous along time with one row pitch each; ``out`` (None: a new tensor) may
+    be ``x`` itself -- a block owns whole columns -- but must not overlap it otherwise.  ``trace`` (None: a new
+    tensor): contiguous fp32 [C, n], receives the value subtracted.  Returns ``(out, trace)``."""
+    from ..data.common_mode import HOWS, as_common_mode
+    how = as_common_mode(how)
+    if how is None:
+        raise ValueError("common_mode needs 'median' or 'mean'")
+    pitch = _time_rows(x, "x")
+    C, Fn, n = x.shape
+    if C < 1 or not 1 <= Fn <= lib().COMMON_MODE_MAX_F:
+        raise ValueError(f"x needs C >= 1 and 1 <= F <= {lib().COMMON_MODE_MAX_F}, got {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty(C, Fn, n, device=x.device)
+    out_pitch = _time_rows(out, "out")
+    if tuple(out.shape) != (C, Fn, n):
+        raise ValueError(f"out must be [{C}, {Fn}, {n}], got {tuple(out.shape)}")
+    if trace is None:
+        trace = torch.empty(C, n, device=x.device)
+    _check(trace, torch.float32)
+    if tuple(trace.shape) != (C, n):
+        raise ValueError(f"trace must be [{C}, {n}], got {tuple(trace.shape)}")
+    tiles = (n + lib().COMMON_MODE_TILE - 1) // lib().COMMON_MODE_TILE
+    if n >= 1 << 31 or C * tiles >= 1 << 31 or C * Fn >= 1 << 32 or max(pitch, out_pitch) >= 1 << 31:
+        raise ValueError(f"x {tuple(x.shape)} is beyond what one launch addresses")
+    if n == 0:
+        return out, trace
+
+    def overlap(p, q):
+        return p[0] < q[1] and q[0] < p[1]
+    xs, os_ = _span(x, (C * Fn - 1) * pitch + n), _span(out, (C * Fn - 1) * out_pitch + n)
+    if (out_pitch != pitch) if out.data_ptr() == x.data_ptr() else overlap(xs, os_):
+        raise ValueError("out must be x itself or apart from it: a block reads what another writes otherwise")
+    ts_ = _span(trace, C * n)
+    if overlap(ts_, xs) or overlap(ts_, os_):
+        raise ValueError("trace must not overlap x or out")
+    lib().common_mode(stream(), {"x": ptr(x), "out": ptr(out), "trace": ptr(trace), "rows": C, "F": Fn, "n": n,
+                                 "pitch": pitch, "out_pitch": out_pitch, "how": HOWS.index(how)})
+    return out, trace

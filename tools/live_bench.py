@@ -15,6 +15,14 @@ adds ``decimate``: the ``fir_decimate`` launch alone on 2,000 * D raw samples pe
 default taps and ``taps = [1]``) beside a device-to-device copy of the same raw bytes timed in the same run -- every
 raw sample has to be read once, so the copy is the floor -- and ``LiveRecording.push`` of that raw chunk from the host
 beside a push of the 2,000 decimated samples without decimation.
+
+    python tools/live_bench.py --common_mode median
+
+adds ``common_mode``: the ``common_mode`` launch alone, in place as the live path runs it, on the chunk shape above
+(``--fiber`` rows of 2,000 columns) and on four times the rows -- the work is linear in the fiber, so the ratio should
+be about 4 -- beside a device-to-device copy of the same bytes (the floor: every sample is read and written once);
+these are device-event times over 20 launches back to back, so the launch overhead of a single call is not in
+them.  Then ``LiveRecording.push`` of the chunk from the host with the stage and without it, alternating.
 """
 import argparse
 import json
@@ -34,6 +42,8 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--ring", type=int, default=4096)
     ap.add_argument("--decimate", type=int, default=None, help="also time the raw-rate front end at this factor")
+    ap.add_argument("--common_mode", choices=["median", "mean"], default=None,
+                    help="also time the common-mode stage with this estimate")
     args = ap.parse_args()
     import torch
     from mtl_das_pytorch_amd.inference import WINDOW, LiveRecording, predict_recording, window_runner
@@ -104,6 +114,8 @@ def main():
     live.close()
     if args.decimate is not None:
         out["decimate"] = decimate_timings(args, m, stride, timed, stats)
+    if args.common_mode is not None:
+        out["common_mode"] = common_mode_timings(args, m, stride, timed, stats)
     print(json.dumps(out))
 
 
@@ -147,6 +159,56 @@ def decimate_timings(args, model, stride, timed, stats):
         nwin = []
         ts = timed(lambda: nwin.append(len(live.push(chunk)["positions"])), 20)
         res[tag] = dict(stats(ts), windows=nwin[-1], samples=chunk.shape[2])
+        live.close()
+    return res
+
+
+def common_mode_timings(args, model, stride, timed, stats):
+    """The common-mode stage with ``--common_mode``: launch and copy floor at F and 4 F rows, and the push with and
+    without it (module docstring)."""
+    import torch
+    from mtl_das_pytorch_amd.inference import LiveRecording
+    from mtl_das_pytorch_amd.ops import functional as HF
+    how, F, n, reps = args.common_mode, args.fiber, 2000, 20
+    g = torch.Generator().manual_seed(3)
+    res = {"how": how, "columns": n, "launches_per_timing": reps}
+
+    def events(fn, rounds=10):
+        """Device time of one ``fn()``, ms: ``reps`` calls back to back between two events, ``rounds`` times."""
+        for _ in range(3):
+            fn()
+        ts = []
+        for _ in range(rounds):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b) / reps / 1e3)
+        return stats(ts)
+    for rows in (F, 4 * F):
+        x = torch.randn(1, rows, n, generator=g).cuda()
+        twin, trace = torch.empty_like(x), torch.empty(1, n, device="cuda")
+        # in place: after the first launch the data is its own residue, still noise of the same spread
+        res[f"launch_F{rows}"] = dict(events(lambda: HF.common_mode(x, how, out=x, trace=trace)), bytes=4 * x.numel())
+        res[f"copy_F{rows}"] = dict(events(lambda: twin.copy_(x)), bytes=4 * x.numel())
+    res["launch_ratio_4F"] = round(res[f"launch_F{4 * F}"]["median_ms"] / res[f"launch_F{F}"]["median_ms"], 3)
+    # push from the host, the stage on and off in alternating groups
+    big_n = n - n % stride[1]
+    chunk = torch.randn(1, F, big_n, generator=g)
+    live_kw = dict(stride=stride, ring=args.ring, batch=args.batch, device="cuda", use_engine=True)
+    lives = {"push_plain": LiveRecording(model, args.model, F, **live_kw),
+             "push_common_mode": LiveRecording(model, args.model, F, common_mode=how, **live_kw)}
+    ts = {k: [] for k in lives}
+    for live in lives.values():
+        for _ in range(4):
+            live.push(chunk)
+    for _ in range(4):
+        for k, live in lives.items():
+            ts[k] += timed(lambda: live.push(chunk), 5)
+    for k, live in lives.items():
+        res[k] = dict(stats(ts[k]), samples=big_n, captures=live.captures)
         live.close()
     return res
 
